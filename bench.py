@@ -8,7 +8,16 @@ Count(Intersect(Row a, Row b)) over every shard: |a_s ∩ b_s| for each shard s
 executor.go:5880) and, for N > 1, the cross-GPU sum of the partial counts by one RCCL
 all-reduce (the exchange step executor.go:6449 mapReduce does over HTTP).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps (`ms_per_step` = that region's wall clock / K), writes the
+outputs of the last timed step if `--dump-outputs DIR` is given, and prints the line.  Everything else below (the
+parity check, the repeated regions, roofline, materialising variant, secondary and strong-scaling configurations,
+N > 1 latency modes, the in-library group path, the CPU baseline) runs only with `--full`.
+
+`--dump-outputs DIR` writes what a caller of the timed path receives after its last step, as float64 .npy files:
+`shard_counts.npy` (|a_s ∩ b_s| of every shard, ranks in order) and `total.npy` (the step's reduced total).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself
 (torch.distributed.run, one rank per GPU, RCCL; when the box has fewer than N GPUs the ranks share
@@ -18,12 +27,12 @@ reads RANK / LOCAL_RANK / WORLD_SIZE as usual.  Prints ONE JSON line on rank 0.
 `value` = container set-ops per second over all N GPUs (a set-op = one container pair with equal
 keys); weak scaling (1024 shards per GPU).  For N > 1 EVERY step carries its own RCCL
 all-reduce of its partial total (one collective per query, pipelined on the device — nothing is amortised
-over several steps; the bucketed throughput mode of the earlier rounds is reported beside it as
-`throughput_mode_bucketed`), and `strong_scaling` holds BASELINE.json configs[3]: the FIXED 8192-shard
+over several steps).  With --full, the bucketed throughput mode of the earlier rounds is reported beside it as
+`throughput_mode_bucketed`, and `strong_scaling` holds BASELINE.json configs[3]: the FIXED 8192-shard
 32 x 32 IntersectionCount matrix (+ filter) split over the N ranks, one all-reduce of the 1024-cell partial
 matrix per query, the host add beside it, and the same query through the in-library group path
-(fbk_group_count_matrix, host / xGMI-peer / RCCL reduce) in `group_api`.  Also in the line: the distribution of
-the step time over repeated timed regions, bits-scanned GB/s, the roofline of the dominant kernel
+(fbk_group_count_matrix, host / xGMI-peer / RCCL reduce) in `group_api`.  Also in the --full line: the distribution of
+the step time over repeated timed regions, the roofline of the dominant kernel
 (HIP events around back-to-back launches), the materialising variant, `secondary` = BASELINE.json
 configs 3, 4 and 5 at their per-GPU sizes (N = 1), for N > 1 the per-step-collective and
 host-add latency modes and the in-library multi-device path (fbk_group_*), and the CPU oracle
@@ -57,6 +66,19 @@ def dist_of(xs):
     v = sorted(xs)
     n = len(v)
     return {"median": v[n // 2], "p10": v[n // 10], "p90": v[min(n - 1, (n * 9) // 10)], "n": n}
+
+
+def dump_outputs(out_dir: str, counts: np.ndarray, total: int, dist=None, rank: int = 0) -> None:
+    """--dump-outputs: this rank's per-shard counts (gathered over the ranks in rank order) and the reduced total of the last
+    timed step, written by rank 0 as float64 (exact: a shard counts at most 2^20 bits)."""
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, counts)
+        counts = np.concatenate(parts)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "shard_counts.npy"), counts.astype(np.float64))
+        np.save(os.path.join(out_dir, "total.npy"), np.array([total], dtype=np.float64))
 
 
 def self_launch(args) -> int:
@@ -771,7 +793,13 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--shards", type=int, default=SHARDS_PER_GPU, help="shards per GPU")
-    ap.add_argument("--repeats", type=int, default=50, help="additional timed regions of --steps steps (distribution of the step time)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (see the module docstring); off: set up, warm up, time --steps steps, "
+                         "write --dump-outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64): shard_counts, total")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="additional timed regions of --steps steps (distribution of the step time); default 50 with --full, 0 without")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip BASELINE configs 3, 4, 5 (N = 1 only anyway)")
     ap.add_argument("--shards3", type=int, default=256)
@@ -784,10 +812,12 @@ def main():
     ap.add_argument("--queries4", type=int, default=10, help="timed queries per reduce mode of the strong-scaling section")
     ap.add_argument("--detail", default="bench_detail.json", help="file name (under the repo root, and gpurun_out/ when present) of the verbose result object; stdout carries the compact line")
     ap.add_argument("--two-contexts", action="store_true",
-                    help="also time two independent queries in flight (root context + fbk_ctx_fork); off by default: its overlapping launches would "
+                    help="with --full, also time two independent queries in flight (root context + fbk_ctx_fork); off by default: its overlapping launches would "
                          "double the per-launch durations a kernel trace of this command shows for the headline kernel")
     ap.add_argument("--cold-sets", type=int, default=4, help="distinct resident data sets cycled for the L3-cold roofline (1 = skip)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 50 if args.full else 0
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
@@ -807,7 +837,7 @@ def main():
     # config 3's rows are generated first, in forked worker processes, BEFORE this process touches the
     # HIP runtime (a fork afterwards would be unsafe)
     pre3 = None
-    if n_gpus == 1 and not args.no_secondary and args.shards3:
+    if n_gpus == 1 and args.full and not args.no_secondary and args.shards3:
         import datagen as D0
 
         t0 = time.perf_counter()
@@ -920,22 +950,34 @@ def main():
         for _ in range(args.warmup):
             step()
         flush()
+        bucket0 = red.cur  # (N = 1) the bucket the first timed step writes its total into
         dt, reduced = timed_region(args.steps)  # THE timed region: exactly --steps steps
 
-        # parity spot check of the timed result (numpy popcount of this rank's shards)
-        local_expected = int(np.bitwise_count(wa & wb).sum())
-        got_counts = counts.cpu().numpy().view(np.uint64)
-        assert int(got_counts.sum()) == local_expected, "GPU result differs from numpy popcount"
-        # every used slot must hold the sum over ranks of the per-rank expected counts
-        ge = torch.tensor([local_expected], dtype=torch.int64, device=dev)
-        if n_gpus > 1:
-            dist.all_reduce(ge)
-        global_expected = int(ge.item())
-        vals = torch.cat([b.reshape(-1) for b in reduced]).cpu().numpy()
-        vals = vals[vals != 0]
-        assert vals.size > 0 and (vals == global_expected).all(), (
-            f"reduced totals differ from the sum of the per-shard counts: expected {global_expected} (this rank {local_expected}), cells "
-            f"{[int(x) for x in torch.cat([b.reshape(-1) for b in reduced]).cpu().numpy()]}")
+        if args.dump_outputs:
+            # the last timed step's outputs: the per-shard counts (overwritten by every step) and the cell its total was reduced into
+            if n_gpus > 1:
+                r = lpq if lib_comm else pq
+                last_total = int(r.buf[(r.k - 1) % PER_QUERY_RING, 0].item())
+            else:
+                j = args.steps - 1
+                last_total = int(red.buf[bucket0 ^ ((j // REDUCE_BUCKET) & 1)][j % REDUCE_BUCKET].item())
+            dump_outputs(args.dump_outputs, counts.cpu().numpy().view(np.uint64), last_total, dist if n_gpus > 1 else None, rank)
+
+        if args.full:
+            # parity spot check of the timed result (numpy popcount of this rank's shards)
+            local_expected = int(np.bitwise_count(wa & wb).sum())
+            got_counts = counts.cpu().numpy().view(np.uint64)
+            assert int(got_counts.sum()) == local_expected, "GPU result differs from numpy popcount"
+            # every used slot must hold the sum over ranks of the per-rank expected counts
+            ge = torch.tensor([local_expected], dtype=torch.int64, device=dev)
+            if n_gpus > 1:
+                dist.all_reduce(ge)
+            global_expected = int(ge.item())
+            vals = torch.cat([b.reshape(-1) for b in reduced]).cpu().numpy()
+            vals = vals[vals != 0]
+            assert vals.size > 0 and (vals == global_expected).all(), (
+                f"reduced totals differ from the sum of the per-shard counts: expected {global_expected} (this rank {local_expected}), cells "
+                f"{[int(x) for x in torch.cat([b.reshape(-1) for b in reduced]).cpu().numpy()]}")
 
         # ---- distribution: the same timed region `repeats` more times (median / p10 / p90 of the step time)
         rep = []
@@ -950,7 +992,7 @@ def main():
         # ---- N > 1: what ONE query pays.  (a) a collective per step, pipelined on the device;
         # (b) the same with the total read back by the host after every step (per-query latency);
         # (c) "copy the partials to the host and add": D2H of each rank's partial + a gloo all-reduce
-        if n_gpus > 1:
+        if n_gpus > 1 and args.full:
             # the bucketed throughput mode of the earlier rounds (REDUCE_BUCKET steps per collective): NOT what a query sees
             saved = (step, flush)
             step, flush = step_bucketed, (lambda: red.flush())
@@ -1011,30 +1053,31 @@ def main():
                 "note": "the headline already carries one all-reduce per step (pipelined over a ring of cells); here the same with ONE cell (each step waits for the previous collective) and with the total read back by the host after every step",
             }
 
-        # ---- roofline of the dominant kernel: HIP events around back-to-back launches
-        # of k_icount_dense alone, on the stream it is launched on
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        kiters = max(args.steps, 50)
-        kernel_step = (lambda: plan.intersection_count_accumulate(total.data_ptr()))  # the launch the timed steps make
-        for _ in range(5):
-            kernel_step()
-        torch.cuda.synchronize()
-        k_samples = []
-        for _ in range(max(10, min(args.repeats, 50))):
-            e0.record(stream)
-            for _ in range(kiters):
+        if args.full:
+            # ---- roofline of the dominant kernel: HIP events around back-to-back launches
+            # of k_icount_dense alone, on the stream it is launched on
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            kiters = max(args.steps, 50)
+            kernel_step = (lambda: plan.intersection_count_accumulate(total.data_ptr()))  # the launch the timed steps make
+            for _ in range(5):
                 kernel_step()
-            e1.record(stream)
             torch.cuda.synchronize()
-            k_samples.append(e0.elapsed_time(e1) / kiters)
-        k_dist = dist_of(k_samples)
-        k_ms = k_dist["median"]
-        alg_bytes = 2 * n * 16 * 8192 + n * 8  # both operands read once + one u64 count per shard
+            k_samples = []
+            for _ in range(max(10, min(args.repeats, 50))):
+                e0.record(stream)
+                for _ in range(kiters):
+                    kernel_step()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                k_samples.append(e0.elapsed_time(e1) / kiters)
+            k_dist = dist_of(k_samples)
+            k_ms = k_dist["median"]
+            alg_bytes = 2 * n * 16 * 8192 + n * 8  # both operands read once + one u64 count per shard
         # ---- the same kernel with the Infinity Cache taken out of the picture: the 256 MiB
         # working set of configs[1] is exactly the size of the 256 MiB L3, so cycle over
         # several distinct resident data sets (cold_sets x 256 MiB) between launches
         cold = None
-        if args.cold_sets > 1:
+        if args.full and args.cold_sets > 1:
             xs = []
             for i in range(1, args.cold_sets):
                 xa = ctx.upload_dense(D.dense_rows(n, 0.5, 5000 + 2 * i + 100 * rank))
@@ -1071,8 +1114,8 @@ def main():
         # 1-3 %: the gap is not idle memory time a second stream can fill.  Opt-in (--two-contexts).
         two_ctx = None
         try:
-            if n_gpus > 1 or not args.two_contexts:
-                raise RuntimeError("N = 1 with --two-contexts only")
+            if n_gpus > 1 or not (args.full and args.two_contexts):
+                raise RuntimeError("N = 1 with --full --two-contexts only")
             ctx2 = ctx.fork()
             stream2 = torch.cuda.Stream(device=dev)
             ctx2.set_stream(stream2.cuda_stream)
@@ -1105,24 +1148,25 @@ def main():
             plan2.free()
             ctx2.close()
         except Exception as e:  # noqa: BLE001 — a secondary figure never fails the run
-            two_ctx = {"error": str(e)[:200]} if (n_gpus == 1 and args.two_contexts) else None
-        # ---- materialising variant: Intersect written out + Count fused (roaring.go:4960)
-        for _ in range(5):
-            plan.setop(L.OP_AND)
-        torch.cuda.synchronize()
-        e0.record(stream)
-        for _ in range(kiters):
-            plan.setop(L.OP_AND)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        m_ms = e0.elapsed_time(e1) / kiters
-        m_bytes = 3 * n * 16 * 8192 + n * 16 * 16 + n * 8
-        plan.total(total.data_ptr())
-        torch.cuda.synchronize()
-        assert int(total.item()) == local_expected
+            two_ctx = {"error": str(e)[:200]} if (n_gpus == 1 and args.full and args.two_contexts) else None
+        if args.full:
+            # ---- materialising variant: Intersect written out + Count fused (roaring.go:4960)
+            for _ in range(5):
+                plan.setop(L.OP_AND)
+            torch.cuda.synchronize()
+            e0.record(stream)
+            for _ in range(kiters):
+                plan.setop(L.OP_AND)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            m_ms = e0.elapsed_time(e1) / kiters
+            m_bytes = 3 * n * 16 * 8192 + n * 16 * 16 + n * 8
+            plan.total(total.data_ptr())
+            torch.cuda.synchronize()
+            assert int(total.item()) == local_expected
 
         strong = None
-        if args.shards4_total:
+        if args.full and args.shards4_total:
             try:
                 cpu_group = dist.new_group(backend="gloo") if n_gpus > 1 else None
                 mine4 = config4_strong(torch, dist if n_gpus > 1 else None, fdist, dev, ctx, stream, rank, n_gpus, args, cpu_group, not args.no_cpu_baseline)
@@ -1158,7 +1202,7 @@ def main():
                     raise  # a rank that left the section early would leave the others in a collective
 
         secondary = None
-        if n_gpus == 1 and not args.no_secondary:
+        if n_gpus == 1 and args.full and not args.no_secondary:
             t_s0 = time.perf_counter()
             try:
                 secondary = secondary_configs(torch, dev, ctx, stream, pre3, args, not args.no_cpu_baseline)
@@ -1177,7 +1221,7 @@ def main():
     # ---- the in-library multi-device path (one process, fbk_group_*): rank 0 runs it in a child process
     # over the same devices while the other ranks wait at the barrier below
     group_api = None
-    if n_gpus > 1 and rank == 0:
+    if args.full and n_gpus > 1 and rank == 0:
         devs = ",".join(str(r if backend == "nccl" else r % n_dev) for r in range(n_gpus))
         try:
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "GROUP_RANK", "ROLE_RANK")}
@@ -1193,7 +1237,7 @@ def main():
             group_api["error"] = "scripts/group_bench.py did not finish within 300 s (killed); modes listed are the ones that completed"
         except Exception as e:  # noqa: BLE001
             group_api = {"error": str(e)}
-    elif n_gpus == 1:
+    elif args.full and n_gpus == 1:
         try:
             group_api = group_in_process(None, wa, wb, local_expected, 50)
         except Exception as e:  # noqa: BLE001
@@ -1202,7 +1246,7 @@ def main():
     # host cores"): rank 0 times it on its own 1024 shards — the N = 1 workload — while the other ranks SLEEP in a gloo
     # barrier (sockets; an RCCL barrier would have every waiting rank spin on a host core the baseline is using)
     cb = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         wait_group = None
         if n_gpus > 1:
             try:
@@ -1221,8 +1265,8 @@ def main():
 
     if rank == 0:
         # the headline: the MEDIAN of the timed regions of exactly --steps steps each (the first one, whose result is parity-checked
-        # above, and the --repeats further ones; every region bracketed by barrier + synchronize, max over ranks): with the driver's
-        # --steps 20 one region is 0.8 ms of wall clock, and a single sample of that moved by 1-2 % from run to run
+        # above with --full, and the --repeats further ones; every region bracketed by barrier + synchronize, max over ranks).  A plain
+        # run has one region: at --steps 20 that is 0.8 ms of wall clock, and a single sample of that moved by 1-2 % from run to run
         regions_ms = sorted([dt / args.steps * 1e3] + list(rep))
         ms_per_step = regions_ms[len(regions_ms) // 2] if len(regions_ms) % 2 else 0.5 * (regions_ms[len(regions_ms) // 2 - 1] + regions_ms[len(regions_ms) // 2])
         henq = sorted(host_enqueue)
@@ -1257,27 +1301,6 @@ def main():
             },
             "ms_per_step_distribution": dict(dist_of(rep), note=f"{args.repeats} further timed regions of {args.steps} steps each") if rep else None,
             "bits_scanned_GBps": n_gpus * 2 * n * 16 * 8192 / (ms_per_step * 1e-3) / 1e9,
-            "roofline": {
-                "kernel": "k_icount_dense<16>",
-                "bound": "hbm",
-                "achieved": alg_bytes / (k_ms * 1e-3) / 1e9,
-                "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s",
-                "frac": alg_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                "traffic": None,
-                "traffic_source": None,
-                "kernel_us": k_ms * 1e3,
-                "kernel_us_distribution": {k: (v * 1e3 if k != "n" else v) for k, v in k_dist.items()},
-                "algorithmic_bytes": alg_bytes,
-            },
-            "materialized": {
-                "kernel": "k_setop_dense<AND>",
-                "set_ops_per_s": n * 16 / (m_ms * 1e-3),
-                "achieved_GBps": m_bytes / (m_ms * 1e-3) / 1e9,
-                "frac": m_bytes / (m_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                "kernel_us": m_ms * 1e3,
-                "algorithmic_bytes": m_bytes,
-            },
             "roofline_l3_cold": cold,
             "two_contexts": two_ctx,
             "h2d_upload_s": t_upload,
@@ -1285,13 +1308,37 @@ def main():
             "h2d_upload_note": "fbk_batch_upload_dense of both operands from pageable numpy memory, end to end (two pinned buffers filled by host threads while the other's DMA runs, recount kernel, descriptor read-back, synchronisation); the pinned buffers exist already (a one-row upload before the clock starts)",
             "group_api": group_api,
         }
+        if args.full:
+            out.update({
+                "roofline": {
+                    "kernel": "k_icount_dense<16>",
+                    "bound": "hbm",
+                    "achieved": alg_bytes / (k_ms * 1e-3) / 1e9,
+                    "peak": HBM_PEAK_GBPS,
+                    "unit": "GB/s",
+                    "frac": alg_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                    "traffic": None,
+                    "traffic_source": None,
+                    "kernel_us": k_ms * 1e3,
+                    "kernel_us_distribution": {k: (v * 1e3 if k != "n" else v) for k, v in k_dist.items()},
+                    "algorithmic_bytes": alg_bytes,
+                },
+                "materialized": {
+                    "kernel": "k_setop_dense<AND>",
+                    "set_ops_per_s": n * 16 / (m_ms * 1e-3),
+                    "achieved_GBps": m_bytes / (m_ms * 1e-3) / 1e9,
+                    "frac": m_bytes / (m_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                    "kernel_us": m_ms * 1e3,
+                    "algorithmic_bytes": m_bytes,
+                },
+            })
         out.update(extra)
         if secondary is not None:
             out["secondary"] = secondary
         if strong is not None:
             out["strong_scaling"] = strong
         traffic_file = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(traffic_file):
+        if args.full and os.path.exists(traffic_file):
             try:
                 out["roofline"]["traffic"] = json.load(open(traffic_file)).get("k_icount_dense_hbm_bytes_per_launch")
                 out["roofline"]["traffic_source"] = "profiles/traffic.json (rocprofv3 --pmc passes of an earlier run of this command, not measured in this run)"

@@ -150,19 +150,20 @@ def compact_line(full: dict, detail_name: str = "bench_detail.json") -> dict:
     if "op" in cfg:
         cfg["op"] = _short(cfg["op"], 200)
     out["config"] = cfg
-    rf = full.get("roofline") or {}
-    out["roofline"] = {
-        "kernel": rf.get("kernel"),
-        "bound": rf.get("bound"),
-        "achieved": _r(rf.get("achieved"), 1),
-        "peak": rf.get("peak"),
-        "unit": rf.get("unit"),
-        "frac": _r(rf.get("frac")),
-        "traffic": rf.get("traffic"),
-        "traffic_source": _short(rf.get("traffic_source"), 120),
-        "kernel_us": _r(rf.get("kernel_us"), 2),
-        "algorithmic_bytes": rf.get("algorithmic_bytes"),
-    }
+    rf = full.get("roofline")
+    if rf:  # (bench.py --full only)
+        out["roofline"] = {
+            "kernel": rf.get("kernel"),
+            "bound": rf.get("bound"),
+            "achieved": _r(rf.get("achieved"), 1),
+            "peak": rf.get("peak"),
+            "unit": rf.get("unit"),
+            "frac": _r(rf.get("frac")),
+            "traffic": rf.get("traffic"),
+            "traffic_source": _short(rf.get("traffic_source"), 120),
+            "kernel_us": _r(rf.get("kernel_us"), 2),
+            "algorithmic_bytes": rf.get("algorithmic_bytes"),
+        }
     cb = full.get("cpu_baseline")
     if cb:
         out["cpu_baseline"] = {

@@ -7,9 +7,9 @@ O=$R/gpurun_out/r6t
 mkdir -p $O
 cd $R
 export TMPDIR=/tmp
-timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; cp bench_detail.json $O/bench_detail.json
+timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; cp bench_detail.json $O/bench_detail.json
 cd /tmp
-timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python $R/bench.py --steps 200 --repeats 5 --no-cpu-baseline > $O/bench_prof.json 2> /dev/null
+timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python $R/bench.py --full --steps 200 --repeats 5 --no-cpu-baseline > $O/bench_prof.json 2> /dev/null
 cd $R
 f=$(find $O/kt -name "*kernel_trace.csv" | head -1); python scripts/kernel_trace_by_grid.py $f 3 > $O/kernel_trace_by_grid.csv
 cp $(find $O/kt -name "*kernel_stats.csv" | head -1) $O/kernel_trace_stats.csv 2>/dev/null

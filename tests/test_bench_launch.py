@@ -32,7 +32,7 @@ def test_world_size_mismatch_is_refused():
 
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
-def test_gpus_2_line_schema_on_the_gpu_box():
+def test_gpus_2_line_schema_on_the_gpu_box(tmp_path):
     """`bench.py --gpus 2` end to end on whatever the box has (one GPU: the two ranks share it and reduce over gloo —
     the complete N > 1 code path, flagged "oversubscribed"): the line must carry the per-query-collective headline,
     the bucketed throughput mode beside it, BASELINE configs[3] strong-scaled (`strong_scaling`) and the in-library
@@ -42,7 +42,7 @@ def test_gpus_2_line_schema_on_the_gpu_box():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     detail = "bench_detail_test_n2.json"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--shards", "128", "--repeats", "2", "--cold-sets", "1",
-           "--shards4-total", "48", "--shards4-mixed-total", "20", "--queries4", "3", "--detail", detail]
+           "--shards4-total", "48", "--shards4-mixed-total", "20", "--queries4", "3", "--detail", detail, "--full", "--dump-outputs", str(tmp_path)]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=850)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stderr[-2000:])
@@ -67,6 +67,45 @@ def test_gpus_2_line_schema_on_the_gpu_box():
     cb = r["cpu_baseline"]
     assert r["roofline"]["frac"] > 0 and cb["kind"] == "port" and cb["unit"] == "set-ops/s" and cb["value"] > 0 and cb["cores"] >= 1
     assert "rank 0" in cb["sample"] and cb["single_thread_set_ops_per_s"] > 0
+    # --dump-outputs: both ranks' per-shard counts of the last timed step, in rank order, and the reduced total
+    _check_dump(tmp_path, 128, 2)
+
+
+def _check_dump(d, shards, n_gpus):
+    """the files --dump-outputs wrote: float64 per-shard counts of every rank's seeded rows (bench.py: seeds 1000 + 2r, 1001 + 2r)
+    and the total reduced over the ranks"""
+    import datagen as D
+    import numpy as np
+
+    exp = np.concatenate([np.bitwise_count(D.dense_rows(shards, 0.5, 1000 + 2 * r) & D.dense_rows(shards, 0.5, 1001 + 2 * r)).sum(axis=(1, 2))
+                          for r in range(n_gpus)])
+    counts, total = np.load(os.path.join(d, "shard_counts.npy")), np.load(os.path.join(d, "total.npy"))
+    assert counts.dtype == np.float64 and total.dtype == np.float64 and total.shape == (1,)
+    assert (counts == exp).all() and int(total[0]) == int(exp.sum())
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: exactly one timed region of K steps, the headline keys, none of the
+    --full sections, and --dump-outputs writes the last step's per-shard counts and total."""
+    import json
+
+    detail = "bench_detail_test_plain.json"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "37", "--warmup", "3", "--shards", "64", "--detail", detail,
+           "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=280)
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stderr[-3000:])
+    os.remove(os.path.join(ROOT, detail))
+    c = json.loads(lines[0])
+    assert c["steps"] == 37 and c["warmup"] == 3 and c["timed_regions"] == 1 and c["n_gpus"] == 1 and c["config"]["shards_per_gpu"] == 64
+    assert c["ms_per_step"] > 0 and c["ms_per_step"] == c["ms_per_step_first_region"] and c["higher_is_better"] is True and c["dtype"] == "u64"
+    assert c["unit"] == "set-ops/s" and abs(c["value"] - 64 * 16 / (c["ms_per_step"] * 1e-3)) <= 1e-3 * c["value"]
+    for k in ("roofline", "cpu_baseline", "secondary", "strong_scaling", "materialized", "ms_per_step_distribution"):
+        assert k not in c, k
+    _check_dump(tmp_path, 64, 1)
 
 
 def _check_compact(c, n, steps, shards4_total):
@@ -105,7 +144,7 @@ def test_gpus_8_oversubscribed_line_on_the_gpu_box():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     detail = "bench_detail_test_n8.json"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "3", "--shards", "32", "--repeats", "2", "--cold-sets", "1",
-           "--shards4-total", "60", "--shards4-mixed-total", "20", "--queries4", "2", "--detail", detail]
+           "--shards4-total", "60", "--shards4-mixed-total", "20", "--queries4", "2", "--detail", detail, "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=850)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     if p.returncode != 0 and os.path.isdir(os.path.join(ROOT, "gpurun_out")):  # (post-mortem: pytest abbreviates the message below)
