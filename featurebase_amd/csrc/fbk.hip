@@ -10,6 +10,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -31,6 +32,7 @@
 #include "fbk_matrix_fused.hip.h"
 #include "fbk_matrix_fused.hip.h"
 #include "fbk_matrix_fusedq.hip.h"
+#include "fbk_matrix_sum.hip.h"
 #include "fbk_wire_kernels.hip.h"
 
 using fbk::Slot;
@@ -1930,6 +1932,7 @@ int32_t fbk_setop(fbk_ctx* ctx, int32_t op, const fbk_batch* a, const uint32_t* 
 }  // extern "C"
 
 #include "fbk_query_api.inc"
+#include "fbk_matrix_sum_api.inc"
 #include "fbk_prepared_api.inc"
 #include "fbk_wire_api.inc"
 #include "fbk_cache_api.inc"

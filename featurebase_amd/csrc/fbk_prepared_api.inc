@@ -14,7 +14,7 @@
 // It is the unit one (query, node) call of mapperLocal (executor.go:6742) becomes when the same query runs again —
 // and what the multi-GPU reduce wants: the partial matrix stays on the device for the collective.
 
-enum FbkQueryKind : int32_t { kQCountMatrix = 1, kQFoldICount = 2, kQBsiSum = 3, kQBsiRangeSum = 4, kQBsiRange = 5, kQFold = 6, kQTopN = 7 };
+enum FbkQueryKind : int32_t { kQCountMatrix = 1, kQFoldICount = 2, kQBsiSum = 3, kQBsiRangeSum = 4, kQBsiRange = 5, kQFold = 6, kQTopN = 7, kQCountMatrixSum = 8 };
 
 struct fbk_query {
   fbk_ctx* ctx = nullptr;
@@ -53,6 +53,8 @@ struct fbk_query {
   // count matrix over encoded rows: the prepared program of the kernel (fbk_matrix_fused.hip.h), built on the first run and again
   // whenever a batch's descriptors have been rewritten since
   FxProgram fx;
+  // GroupBy with aggregate=Sum (fbk_matrix_sum_api.inc): row lists, scratch and the result {sums, counts}
+  std::unique_ptr<MsumPlan> msum;
 };
 
 namespace {
@@ -133,6 +135,33 @@ int32_t fbk_query_count_matrix(fbk_ctx* ctx, const fbk_batch* a, const uint32_t*
     const hipError_t e = q->result.alloc(ctx, q->result_bytes);
     if (e != hipSuccess) rc = fail(FBK_E_NOMEM, std::string("query: ") + hipGetErrorString(e));
   }
+  return query_finish_create(ctx, q, rc, out_query);
+} FBK_ABI_CATCH(ctx)
+
+int32_t fbk_query_count_matrix_sum(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b, const uint32_t* rows_b,
+                                   uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f, const fbk_batch* bsi, const uint32_t* base_rows,
+                                   uint32_t bit_depth, uint32_t n_shards, fbk_query** out_query) try {
+  FBK_ENTER(ctx);
+  if (!ctx || !a || !out_query) return fail(FBK_E_INVALID, "NULL argument");
+  *out_query = nullptr;
+  if (int32_t rc = msum_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
+  if (n_shards == 0 || n_a == 0 || n_b == 0) return fail(FBK_E_INVALID, "query: empty count matrix");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+  fbk_query* q = new (std::nothrow) fbk_query();
+  if (!q) return fail(FBK_E_NOMEM, "host allocation failed");
+  q->ctx = ctx;
+  q->kind = kQCountMatrixSum;
+  q->a = a;
+  q->b = b;
+  q->filter = filter;
+  q->n_a = n_a;
+  q->n_b = n_b;
+  q->n = n_shards;
+  q->depth = bit_depth;
+  q->result_bytes = uint64_t(n_a) * n_b * 16;
+  q->msum.reset(new MsumPlan());
+  const int32_t rc = msum_prepare(ctx, *q->msum, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards);
   return query_finish_create(ctx, q, rc, out_query);
 } FBK_ABI_CATCH(ctx)
 
@@ -374,6 +403,11 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
                                          static_cast<u64*>(out), q->dr, acc, recs, &q->fx);
       break;
     }
+    case kQCountMatrixSum:
+      if (acc || device_out) return fail(FBK_E_INVALID, "query: a GroupBy Sum writes its own two arrays (fbk_query_read), nothing to accumulate");
+      rc = msum_enqueue(ctx, *q->msum);
+      if (!rc) out = q->msum->result.p;
+      break;
     case kQFoldICount: {
       const Slot* recs = nullptr;
       if (q->op != FBK_OP_AND) rc = query_row_records(ctx, q, q->n, q->k, &recs);  // (the scatter kernels)
@@ -456,7 +490,7 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
 int32_t fbk_query_result(fbk_ctx* ctx, fbk_query* q, void** out_device_ptr, uint64_t* out_bytes) try {
   FBK_ENTER(ctx);
   if (int32_t rc = query_check(ctx, q)) return rc;
-  if (out_device_ptr) *out_device_ptr = q->result.p;
+  if (out_device_ptr) *out_device_ptr = q->msum ? q->msum->result.p : q->result.p;  // (GroupBy Sum: {sums, counts})
   if (out_bytes) *out_bytes = q->result_bytes;
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
@@ -477,6 +511,8 @@ int32_t fbk_query_read(fbk_ctx* ctx, fbk_query* q, void* out0, void* out1) try {
       HIP_TRY(back.finish());
       return FBK_OK;
     }
+    case kQCountMatrixSum:  // out0 = int64 sums [n_a * n_b], out1 = uint64 counts [n_a * n_b]
+      return msum_read(ctx, *q->msum, static_cast<int64_t*>(out0), static_cast<uint64_t*>(out1));
     case kQFoldICount:
     case kQBsiRange:  // out0 = the per-shard cardinalities of the result rows
     case kQFold:      // out0 = the per-group cardinalities

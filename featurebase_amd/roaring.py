@@ -221,6 +221,11 @@ class Query:
             ps = np.zeros((n_shards, n_a, n_b), dtype=np.uint64) if per_shard else None
             L.check(self.ctx.lib.fbk_query_read(self.ctx.h, self.h, tot.ctypes.data, ps.ctypes.data if ps is not None else None))
             return (tot, ps) if per_shard else tot
+        if self.kind == "count_matrix_sum":  # (sums [n_a, n_b] int64, counts [n_a, n_b] uint64)
+            _, n_a, n_b = self.shape
+            sums, counts = np.zeros((n_a, n_b), dtype=np.int64), np.zeros((n_a, n_b), dtype=np.uint64)
+            L.check(self.ctx.lib.fbk_query_read(self.ctx.h, self.h, sums.ctypes.data, counts.ctypes.data))
+            return sums, counts
         if self.kind in ("fold", "rows"):  # counts per group / cardinalities of the result rows
             out = np.zeros(self.shape[0], dtype=np.uint64)
             L.check(self.ctx.lib.fbk_query_read(self.ctx.h, self.h, out.ctypes.data, None))
@@ -617,6 +622,40 @@ class Context:
             )
         )
         return (tot, ps) if per_shard else tot
+
+    # -- GroupBy with aggregate=Sum ------------------------------------------------------------
+    def _msum_args(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, filt: Optional[Batch], rows_f):
+        ra = np.ascontiguousarray(rows_a, dtype=np.uint32)
+        n_shards, n_a = ra.shape
+        rb = np.ascontiguousarray(rows_b, dtype=np.uint32).reshape(n_shards, -1) if b is not None else None
+        n_b = rb.shape[1] if rb is not None else 1
+        base = np.ascontiguousarray(base_rows, dtype=np.uint32)
+        assert base.size == n_shards
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        args = (self.h, a.h, ra.ctypes.data, n_a, b.h if b is not None else None, rb.ctypes.data if rb is not None else None, n_b,
+                filt.h if filt is not None else None, rf.ctypes.data if rf is not None else None, bsi.h, base.ctypes.data)
+        return args, (ra, rb, base, rf), n_shards, n_a, n_b
+
+    def count_matrix_sum(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, bit_depth: int,
+                         filt: Optional[Batch] = None, rows_f=None) -> Tuple[np.ndarray, np.ndarray]:
+        """GroupBy(..., aggregate=Sum(field)) of the last two levels: for every pair (i, j) the BSI sum and the count over
+        A_i ∩ B_j ∩ filt ∩ exists, summed over the shards (b = None: the one-field form, one column).
+        rows_a [n_shards, n_a], rows_b [n_shards, n_b], base_rows / rows_f [n_shards].  Returns (sums int64, counts uint64),
+        both [n_a, n_b]; the caller adds count * Base."""
+        args, keep, n_shards, n_a, n_b = self._msum_args(a, rows_a, b, rows_b, bsi, base_rows, filt, rows_f)
+        sums, counts = np.zeros((n_a, n_b), dtype=np.int64), np.zeros((n_a, n_b), dtype=np.uint64)
+        L.check(self.lib.fbk_count_matrix_sum(*args, bit_depth, n_shards, sums.ctypes.data, counts.ctypes.data))
+        del keep
+        return sums, counts
+
+    def query_count_matrix_sum(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, bit_depth: int,
+                               filt: Optional[Batch] = None, rows_f=None) -> Query:
+        """count_matrix_sum as a prepared, launch-only query; read() returns (sums, counts)"""
+        args, keep, n_shards, n_a, n_b = self._msum_args(a, rows_a, b, rows_b, bsi, base_rows, filt, rows_f)
+        h = C.c_void_p()
+        L.check(self.lib.fbk_query_count_matrix_sum(*args, bit_depth, n_shards, C.byref(h)))
+        del keep
+        return Query(self, h.value, "count_matrix_sum", (n_shards, n_a, n_b))
 
     # -- prepared (launch-only) forms of the query-level calls -------------------------------
     def prepare_count_matrix(self, a: Batch, rows_a, b: Batch, rows_b, filt: Optional[Batch] = None, rows_f=None, keep_per_shard: bool = False) -> Query:

@@ -517,6 +517,30 @@ int32_t fbk_count_matrix(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_
                          const uint32_t* rows_f, uint32_t n_shards, uint64_t* out_total,
                          uint64_t* out_per_shard);
 
+/* ---- GroupBy with aggregate=Sum(field=v) ------------------------------------------------------
+ * For every pair (i, j), summed over the shards given (X = A.rows_a[s*n_a+i] ∩ B.rows_b[s*n_b+j] ∩ F.rows_f[s] ∩ exists):
+ *   out_counts[i*n_b+j] = Σ_s |X|
+ *   out_sums[i*n_b+j]   = Σ_s Σ_k 2^k (|X ∩ ¬sign ∩ plane_k| − |X ∩ sign ∩ plane_k|), uint64 wrap-around as fbk_bsi_sum
+ * i.e. fbk_bsi_sum over the filter A_i ∩ B_j ∩ F, summed over the shards, for all pairs at once: groupByIterator.Next's
+ * executeSumCountShard per group (executor.go:8880-8913, 2155-2216).  The caller adds count * Base (executor.go:2206).
+ * The BSI layout is fbk_bsi_sum's (base_rows[s] + 0 exists, + 1 sign, + 2 + k plane k); bits of the sign or a plane outside
+ * exists contribute nothing.  b == NULL is the one-field GroupBy: n_b must be 1 and X = A_i ∩ F ∩ exists.  filter == NULL:
+ * no filter.  bit_depth 0..64; n_a, n_b <= 4096.  Row lists [n_shards][n_a], [n_shards][n_b], [n_shards], [n_shards].
+ * One matrix-core pass per shard over dense rows; rows of batches that are not dense are densified first, a chunk of shards
+ * at a time: most = max(1, min(n_shards, 2^30 / per_shard)) with per_shard = ceil(bit_depth / 7) * 2^20 + 16 * n_a * n_b
+ * + 2^17 * (the rows densified per shard: n_a if A is not dense, n_b if B is not, 1 if the filter is not, bit_depth + 2 if
+ * the BSI batch is not); chunk = ceil(n_shards / ceil(n_shards / most)), the shards dealt evenly over the fewest chunks.
+ * fbk_query_count_matrix_sum is the prepared form: fbk_query_run takes no device_out and no FBK_QUERY_ACCUMULATE;
+ * fbk_query_read(q, out0, out1) gives the int64 sums [n_a*n_b] in out0 and the uint64 counts [n_a*n_b] in out1. */
+int32_t fbk_count_matrix_sum(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
+                             const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
+                             const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
+                             int64_t* out_sums, uint64_t* out_counts);
+int32_t fbk_query_count_matrix_sum(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
+                                   const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
+                                   const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
+                                   fbk_query** out_query);
+
 /* ---- BSI (bit-sliced integers) ----------------------------------------------------------------
  * A BSI fragment of shard s occupies bit_depth+2 consecutive rows of `batch` starting at
  * base_rows[s]: +0 exists, +1 sign, +2+i magnitude bit i (fragment.go:62-65). */

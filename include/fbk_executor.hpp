@@ -689,29 +689,54 @@ class Executor {
       }
     return rows;
   }
-  bool emit(const std::vector<FieldRow>& group, uint64_t count, const RowSet* members, const std::string& agg_field, uint64_t limit,
-            std::vector<GroupCount>& out) {
+  bool emit(const std::vector<FieldRow>& group, uint64_t count, int64_t agg, uint64_t limit, std::vector<GroupCount>& out) {
+    if (count == 0) return true;  // groupByIterator.Next skips Count == 0 (executor.go:8905-8913)
     GroupCount g;
     g.Group = group;
     g.Count = count;
-    if (!agg_field.empty()) {  // aggregate=Sum(field): Count is the number of columns WITH a value (executor.go:8905-8913)
-      const Index::IntField& f = idx_.ints_.at(agg_field);
-      std::vector<uint32_t> base = base_rows(f);
-      const size_t n = base.size();
-      std::vector<int64_t> sums(n);
-      std::vector<uint64_t> counts(n);
-      check(fbk_bsi_sum(idx_.ctx_, f.batch, base.data(), uint32_t(n), f.bit_depth, members->batch(), members->rows().data(), sums.data(), counts.data()));
-      ValCount v;
-      for (size_t s = 0; s < n; ++s) v = v.Add({sums[s] + int64_t(counts[s]) * f.base, int64_t(counts[s])});
-      g.Count = uint64_t(v.Count);
-      g.Agg = v.Val;
-    }
-    if (g.Count == 0) return true;
+    g.Agg = agg;
     out.push_back(std::move(g));
     return !(limit && out.size() >= limit);
   }
-  // fields[level..]: the last two levels are one count-matrix call; earlier levels materialise
-  // prefix ∩ row (gbi.rows[i].row.Intersect(gbi.rows[i-1].row), executor.go:8829-8834)
+  // aggregate=Sum(field) of the last level (b == nullptr) or the last two levels: fbk_count_matrix_sum, the prefix row (if any)
+  // as the filter — ONE call when both fields have at most kSumBlock rows, otherwise one call per block of kSumBlock x kSumBlock
+  // rows (the call's limit per side; fbk_count / fbk_count_matrix take up to 2^22 rows against one).  counts[i * nb + j] =
+  // columns WITH a value (the group's Count), sums + count * Base = its Agg (executeSumCountShard per group, executor.go:2155-2216).
+  static constexpr size_t kSumBlock = 4096;
+  void sum_matrix(const std::string& agg_field, const Index::SetField& fa, const std::vector<uint32_t>& rows_a, const Index::SetField* fb,
+                  const std::vector<uint32_t>* rows_b, const RowSet* prefix, std::vector<int64_t>& agg, std::vector<uint64_t>& counts) {
+    const Index::IntField& f = idx_.ints_.at(agg_field);
+    std::vector<uint32_t> base = base_rows(f);
+    const size_t n = base.size(), na = fa.row_ids.size(), nb = fb ? fb->row_ids.size() : 1;
+    agg.assign(na * nb, 0);
+    counts.assign(na * nb, 0);
+    // the rows [k0, k0 + bk) of every shard of a [n][nk] row list
+    auto block = [n](const std::vector<uint32_t>& rows, size_t nk, size_t k0, size_t bk) {
+      if (k0 == 0 && bk == nk) return rows;
+      std::vector<uint32_t> out(n * bk);
+      for (size_t s = 0; s < n; ++s) std::copy(rows.begin() + s * nk + k0, rows.begin() + s * nk + k0 + bk, out.begin() + s * bk);
+      return out;
+    };
+    for (size_t i0 = 0; i0 < na; i0 += kSumBlock)
+      for (size_t j0 = 0; j0 < nb; j0 += kSumBlock) {
+        const size_t bi = std::min(kSumBlock, na - i0), bj = std::min(kSumBlock, nb - j0);
+        const std::vector<uint32_t> ra = block(rows_a, na, i0, bi);
+        const std::vector<uint32_t> rb = fb ? block(*rows_b, nb, j0, bj) : std::vector<uint32_t>();
+        std::vector<int64_t> sums(bi * bj);
+        std::vector<uint64_t> cnt(bi * bj);
+        check(fbk_count_matrix_sum(idx_.ctx_, fa.batch, ra.data(), uint32_t(bi), fb ? fb->batch : nullptr, fb ? rb.data() : nullptr, uint32_t(bj),
+                                   prefix ? prefix->batch() : nullptr, prefix ? prefix->rows().data() : nullptr, f.batch, base.data(), f.bit_depth,
+                                   uint32_t(n), sums.data(), cnt.data()));
+        for (size_t i = 0; i < bi; ++i)
+          for (size_t j = 0; j < bj; ++j) {
+            const size_t k = (i0 + i) * nb + j0 + j;
+            counts[k] = cnt[i * bj + j];
+            agg[k] = int64_t(uint64_t(sums[i * bj + j]) + counts[k] * uint64_t(f.base));
+          }
+      }
+  }
+  // fields[level..]: the last two levels are one count-matrix call (one count-matrix-sum call with an aggregate); earlier levels
+  // materialise prefix ∩ row (gbi.rows[i].row.Intersect(gbi.rows[i-1].row), executor.go:8829-8834)
   bool group_by_rec(const std::vector<std::string>& fields, size_t level, const RowSet* prefix, const std::string& agg_field, uint64_t limit,
                     std::vector<FieldRow>& group, std::vector<GroupCount>& out) {
     const size_t n = shards().size();
@@ -722,7 +747,10 @@ class Executor {
     const size_t remaining = fields.size() - level;
     if (remaining == 1) {
       std::vector<uint64_t> tot(na, 0);
-      if (prefix) {
+      std::vector<int64_t> agg(na, 0);
+      if (!agg_field.empty()) {
+        sum_matrix(agg_field, fa, rows_a, nullptr, nullptr, prefix, agg, tot);
+      } else if (prefix) {
         check(fbk_count_matrix(idx_.ctx_, fa.batch, rows_a.data(), uint32_t(na), prefix->batch(), prefix->rows().data(), 1, nullptr, nullptr,
                                uint32_t(n), tot.data(), nullptr));
       } else {
@@ -734,18 +762,7 @@ class Executor {
       for (size_t i = 0; i < na; ++i) {
         if (!tot[i]) continue;
         group.push_back({fields[level], fa.row_ids[i]});
-        bool go = true;
-        if (agg_field.empty()) {
-          go = emit(group, tot[i], nullptr, agg_field, limit, out);
-        } else {
-          RowSet r = leaf_row(fields[level], fa.row_ids[i]);
-          if (prefix) {
-            RowSet m = setop(FBK_OP_AND, r, *prefix);
-            go = emit(group, tot[i], &m, agg_field, limit, out);
-          } else {
-            go = emit(group, tot[i], &r, agg_field, limit, out);
-          }
-        }
+        const bool go = emit(group, tot[i], agg[i], limit, out);
         group.pop_back();
         if (!go) return false;
       }
@@ -757,26 +774,18 @@ class Executor {
       if (nb == 0) return true;
       std::vector<uint32_t> rows_b = field_rows(fb);
       std::vector<uint64_t> tot(na * nb, 0);
-      check(fbk_count_matrix(idx_.ctx_, fa.batch, rows_a.data(), uint32_t(na), fb.batch, rows_b.data(), uint32_t(nb), prefix ? prefix->batch() : nullptr,
-                             prefix ? prefix->rows().data() : nullptr, uint32_t(n), tot.data(), nullptr));
+      std::vector<int64_t> agg(na * nb, 0);
+      if (!agg_field.empty())
+        sum_matrix(agg_field, fa, rows_a, &fb, &rows_b, prefix, agg, tot);
+      else
+        check(fbk_count_matrix(idx_.ctx_, fa.batch, rows_a.data(), uint32_t(na), fb.batch, rows_b.data(), uint32_t(nb), prefix ? prefix->batch() : nullptr,
+                               prefix ? prefix->rows().data() : nullptr, uint32_t(n), tot.data(), nullptr));
       for (size_t i = 0; i < na; ++i)
         for (size_t j = 0; j < nb; ++j) {
           if (!tot[i * nb + j]) continue;
           group.push_back({fields[level], fa.row_ids[i]});
           group.push_back({fields[level + 1], fb.row_ids[j]});
-          bool go = true;
-          if (agg_field.empty()) {
-            go = emit(group, tot[i * nb + j], nullptr, agg_field, limit, out);
-          } else {
-            RowSet ra = leaf_row(fields[level], fa.row_ids[i]), rb = leaf_row(fields[level + 1], fb.row_ids[j]);
-            RowSet m = setop(FBK_OP_AND, ra, rb);
-            if (prefix) {
-              RowSet m2 = setop(FBK_OP_AND, m, *prefix);
-              go = emit(group, tot[i * nb + j], &m2, agg_field, limit, out);
-            } else {
-              go = emit(group, tot[i * nb + j], &m, agg_field, limit, out);
-            }
-          }
+          const bool go = emit(group, tot[i * nb + j], agg[i * nb + j], limit, out);
           group.pop_back();
           group.pop_back();
           if (!go) return false;
