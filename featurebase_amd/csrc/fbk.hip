@@ -33,6 +33,7 @@
 #include "fbk_matrix_fused.hip.h"
 #include "fbk_matrix_fusedq.hip.h"
 #include "fbk_matrix_sum.hip.h"
+#include "fbk_matrix_distinct.hip.h"
 #include "fbk_wire_kernels.hip.h"
 
 using fbk::Slot;
@@ -1933,6 +1934,7 @@ int32_t fbk_setop(fbk_ctx* ctx, int32_t op, const fbk_batch* a, const uint32_t* 
 
 #include "fbk_query_api.inc"
 #include "fbk_matrix_sum_api.inc"
+#include "fbk_matrix_distinct_api.inc"
 #include "fbk_prepared_api.inc"
 #include "fbk_wire_api.inc"
 #include "fbk_cache_api.inc"

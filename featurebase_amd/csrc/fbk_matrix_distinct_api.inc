@@ -1,0 +1,168 @@
+// fbk_matrix_distinct_api.inc — fbk_count_matrix_distinct: GroupBy with aggregate=Count(Distinct(field=v)) for all (A row, B row)
+// groups in one call (fbk_matrix_distinct.hip.h).  Included by fbk.hip after fbk_matrix_sum_api.inc, whose argument checks and
+// count pass it reuses.
+//
+// Three stages on the context's stream:
+//   1. the sorted distinct values U of exists ∩ F over all shards (bsi_distinct_device: fbk_bsi_distinct's kernels, unchanged);
+//   2. per tile of the presence bitmap, k_mdist_scatter over the operands of every shard, then k_mdist_popcount;
+//   3. (out_counts) fbk_count_matrix_sum's count pass: k_msum_mfma without value chunks, exists as the bit planes' row.
+// Operands of batches that are not dense are densified a chunk of shards at a time (k_densify_rows): in stage 1 by
+// bsi_distinct_device (the BSI rows and the filter), in stage 2 again (every operand; stage 2 needs U first), in stage 3 by the
+// count pass.  Stage 2's arithmetic (fbk.h documents it: the tests rely on it):
+//   presence tile: wb = ceil(n_b / 64) words per (A row, rank), m64 = m rounded up to 64, row = 8 * wb * m64 bytes per A row;
+//     n_a * row <= kMdistPresence: one tile;  else 64 * row <= kMdistPresence: ta = floor(kMdistPresence / row) rounded down
+//     to a multiple of 64 A rows, all ranks;  else ta = min(n_a, 64) A rows, tr = floor(kMdistPresence / (8 * wb * ta))
+//     rounded down to a multiple of 64 ranks.
+//   densify chunk: per shard 128 KiB per densified row (n_a, n_b, 1 filter row, depth + 2 BSI rows, each for the batches that
+//     are not dense); most = max(1, min(n_shards, kMdistScratch / that)), chunk = ceil(n_shards / ceil(n_shards / most)).
+//     With more than one chunk, every tile densifies every chunk again.
+
+namespace {
+
+constexpr uint64_t kMdistPresence = 128ull << 20;
+constexpr uint64_t kMdistScratch = 1ull << 30;
+
+struct MdistTiles {
+  uint32_t ta = 0;  // A rows per tile
+  uint64_t tr = 0;  // ranks per tile (a multiple of 64)
+};
+
+MdistTiles mdist_tiles(uint32_t n_a, uint32_t n_b, uint64_t m) {
+  const uint64_t wb = (uint64_t(n_b) + 63) / 64, m64 = (m + 63) / 64 * 64, row = 8 * wb * m64;
+  MdistTiles t;
+  if (uint64_t(n_a) * row <= kMdistPresence) {
+    t.ta = n_a, t.tr = m64;
+  } else if (64 * row <= kMdistPresence) {
+    t.ta = uint32_t(kMdistPresence / row / 64 * 64), t.tr = m64;
+  } else {
+    t.ta = std::min<uint32_t>(n_a, 64), t.tr = kMdistPresence / (8 * wb * t.ta) / 64 * 64;
+  }
+  return t;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
+                                  const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
+                                  const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
+                                  uint64_t* out_distinct, uint64_t* out_counts) try {
+  FBK_ENTER(ctx);
+  if (!ctx || !a || !out_distinct) return fail(FBK_E_INVALID, "NULL argument");
+  if (int32_t rc = msum_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
+  const uint64_t width = uint64_t(n_a) * n_b;
+  std::memset(out_distinct, 0, width * 8);
+  if (out_counts) std::memset(out_counts, 0, width * 8);
+  if (n_shards == 0 || width == 0) return FBK_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+  // stage 1: U
+  DevBuf duniq;
+  u64 m = 0;
+  if (int32_t rc = bsi_distinct_device(ctx, bsi, base_rows, n_shards, bit_depth, filter, rows_f, duniq, m)) return rc;
+  if (m > 0) {
+    // stage 2: operands (densified a chunk of shards at a time), presence tiles
+    const bool da = !a->dense, db = b && !b->dense, df = filter && !filter->dense, dbsi = !bsi->dense;
+    const uint64_t row_bytes = uint64_t(fbk::kSlots) * 8192, rps = uint64_t(bit_depth) + 2;
+    const uint64_t per_shard = row_bytes * ((da ? n_a : 0) + (db ? n_b : 0) + (df ? 1 : 0) + (dbsi ? rps : 0));
+    const uint64_t most = per_shard ? std::max<uint64_t>(1, std::min<uint64_t>(n_shards, kMdistScratch / per_shard)) : n_shards;
+    const uint64_t passes = (n_shards + most - 1) / most;
+    const uint32_t chunk = uint32_t((n_shards + passes - 1) / passes);
+    std::vector<uint32_t> ia(da ? uint64_t(chunk) * n_a : 0), ib(db ? uint64_t(chunk) * n_b : 0), i1(chunk), ibase(dbsi ? chunk : 0),
+        all(dbsi ? uint64_t(n_shards) * rps : 0);
+    for (uint64_t i = 0; i < ia.size(); ++i) ia[i] = uint32_t(i);
+    for (uint64_t i = 0; i < ib.size(); ++i) ib[i] = uint32_t(i);
+    for (uint32_t i = 0; i < chunk; ++i) i1[i] = i;
+    for (uint64_t i = 0; i < ibase.size(); ++i) ibase[i] = uint32_t(i * rps);
+    for (uint32_t s = 0; s < n_shards && dbsi; ++s)
+      for (uint64_t r = 0; r < rps; ++r) all[uint64_t(s) * rps + r] = uint32_t(base_rows[s] + r);
+    DevBuf rows, ta, tb, tf, tbsi, pres, result;
+    const uint32_t* d[9];
+    if (int32_t rc = upload_rows_multi(ctx,
+                                       {{rows_a, uint64_t(n_shards) * n_a, UINT32_MAX},
+                                        {rows_b, b ? uint64_t(n_shards) * n_b : 0, UINT32_MAX},
+                                        {rows_f, filter ? uint64_t(n_shards) : 0, UINT32_MAX},
+                                        {base_rows, n_shards, UINT32_MAX},
+                                        {ia.data(), ia.size(), UINT32_MAX},
+                                        {ib.data(), ib.size(), UINT32_MAX},
+                                        {i1.data(), i1.size(), UINT32_MAX},
+                                        {ibase.data(), ibase.size(), UINT32_MAX},
+                                        {all.data(), all.size(), UINT32_MAX}},
+                                       rows, d))
+      return rc;
+    if (da) HIP_TRY(ta.alloc(ctx, uint64_t(chunk) * n_a * row_bytes));
+    if (db) HIP_TRY(tb.alloc(ctx, uint64_t(chunk) * n_b * row_bytes));
+    if (df) HIP_TRY(tf.alloc(ctx, uint64_t(chunk) * row_bytes));
+    if (dbsi) HIP_TRY(tbsi.alloc(ctx, uint64_t(chunk) * rps * row_bytes));
+    const MdistTiles t = mdist_tiles(n_a, n_b, m);
+    const uint32_t wb = (n_b + 63) / 64, tr = uint32_t(t.tr);
+    const uint64_t m64 = (m + 63) / 64 * 64;
+    HIP_TRY(pres.alloc(ctx, uint64_t(t.ta) * wb * tr * 8));
+    HIP_TRY(result.alloc(ctx, width * 8));
+    HIP_TRY(hipMemsetAsync(result.p, 0, width * 8, ctx->stream));
+    bool densified = false;  // (one chunk: its operands are densified once for all the tiles)
+    for (uint32_t a0 = 0; a0 < n_a; a0 += t.ta) {
+      const uint32_t na = std::min(t.ta, n_a - a0);
+      for (uint64_t r0 = 0; r0 < m64; r0 += tr) {
+        HIP_TRY(hipMemsetAsync(pres.p, 0, uint64_t(na) * wb * tr * 8, ctx->stream));
+        for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
+          const uint32_t ns = std::min(chunk, n_shards - s0);
+          const uint8_t *arA = a->d_arena, *arB = b ? b->d_arena : nullptr, *arF = filter ? filter->d_arena : nullptr, *arS = bsi->d_arena;
+          const uint32_t *ra = d[0] + uint64_t(s0) * n_a, *rb = b ? d[1] + uint64_t(s0) * n_b : nullptr, *rf = filter ? d[2] + s0 : nullptr,
+                         *rs = d[3] + s0;
+          std::vector<fbk::DensifySrc> srcs;
+          if (da) {
+            srcs.push_back({a->d_slots, a->d_arena, ra, uint64_t(ns) * n_a, ta.as<uint8_t>()});
+            arA = ta.as<uint8_t>(), ra = d[4];
+          }
+          if (db) {
+            srcs.push_back({b->d_slots, b->d_arena, rb, uint64_t(ns) * n_b, tb.as<uint8_t>()});
+            arB = tb.as<uint8_t>(), rb = d[5];
+          }
+          if (df) {
+            srcs.push_back({filter->d_slots, filter->d_arena, rf, uint64_t(ns), tf.as<uint8_t>()});
+            arF = tf.as<uint8_t>(), rf = d[6];
+          }
+          if (dbsi) {
+            srcs.push_back({bsi->d_slots, bsi->d_arena, d[8] + uint64_t(s0) * rps, uint64_t(ns) * rps, tbsi.as<uint8_t>()});
+            arS = tbsi.as<uint8_t>(), rs = d[7];
+          }
+          for (size_t k0 = 0; k0 < srcs.size() && !densified; k0 += 3) {
+            fbk::DensifyArgs dargs{};
+            uint64_t cells = 0;
+            for (size_t k = k0; k < std::min(srcs.size(), k0 + 3); ++k) {
+              dargs.src[k - k0] = srcs[k];
+              cells += srcs[k].n_rows * fbk::kSlots;
+            }
+            hipLaunchKernelGGL(fbk::k_densify_rows, dim3(uint32_t((cells + 3) / 4)), dim3(256), 0, ctx->stream, dargs);
+          }
+          densified = passes == 1;
+          const uint64_t units = uint64_t(ns) * (fbk::kSlots * 1024 / fbk::kMdistWords);
+          const uint32_t grid = uint32_t(std::min<uint64_t>((units + 3) / 4, 2048));
+          hipLaunchKernelGGL(fbk::k_mdist_scatter, dim3(grid), dim3(256), 0, ctx->stream, arA, ra, n_a, a0, na, arB, rb, n_b, arF, rf, arS, rs,
+                             bit_depth, duniq.as<long long>(), uint32_t(m), uint32_t(r0), tr, ns, pres.as<u64>());
+        }
+        // popcount: enough parts of the rank range for ~8192 wavefronts
+        const uint64_t pairs = uint64_t(na) * wb;
+        const uint32_t splits = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(tr / 64, 8192 / pairs)));
+        hipLaunchKernelGGL(fbk::k_mdist_popcount, dim3(uint32_t((pairs * splits + 3) / 4)), dim3(256), 0, ctx->stream, pres.as<u64>(), na, n_b,
+                           tr, a0, splits, result.as<u64>());
+      }
+    }
+    HIP_TRY(hipGetLastError());
+    D2H back(ctx);
+    HIP_TRY(back.add(out_distinct, result.p, width * 8));
+    HIP_TRY(back.finish());
+  }
+  if (out_counts) {
+    // stage 3: the columns of every group, fbk_count_matrix_sum's pass at depth 0
+    MsumPlan p;
+    if (int32_t rc = msum_prepare(ctx, p, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, 0, n_shards)) return rc;
+    if (int32_t rc = msum_enqueue(ctx, p)) return rc;
+    if (int32_t rc = msum_read(ctx, p, nullptr, out_counts)) return rc;
+  }
+  return FBK_OK;
+} FBK_ABI_CATCH(ctx)
+
+}  // extern "C"

@@ -1697,18 +1697,12 @@ static uint32_t bsi_values_split(uint32_t n_shards) {
   return split;
 }
 
-int32_t fbk_bsi_distinct(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
-                         uint32_t bit_depth, const fbk_batch* filter, const uint32_t* rows_f, int64_t* out_values,
-                         uint64_t cap, uint64_t* out_n) try {
-  FBK_ENTER(ctx);
-  if (!ctx || !batch || !out_n || (n_shards && !base_rows) || (filter && n_shards && !rows_f) || (cap && !out_values))
-    return fail(FBK_E_INVALID, "NULL argument");
-  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
-  *out_n = 0;
-  if (n_shards == 0) return FBK_OK;
+// The device half of fbk_bsi_distinct: the sorted distinct values of exists ∩ filter over the shards, left on the device in `duniq`
+// (n_unique of them).  Also the first stage of fbk_count_matrix_distinct.  The caller holds ctx->mu and has checked the pointers.
+static int32_t bsi_distinct_device(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards, uint32_t bit_depth,
+                                   const fbk_batch* filter, const uint32_t* rows_f, DevBuf& duniq, u64& n_unique) {
+  n_unique = 0;
   fbk_batch* bb = const_cast<fbk_batch*>(batch);
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
   if (int32_t rc = refresh_slots(bb)) return rc;
   uint64_t upper = 0;  // at most one value per existing column
   for (uint32_t s = 0; s < n_shards; ++s) {
@@ -1720,7 +1714,7 @@ int32_t fbk_bsi_distinct(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* b
     if (int32_t rc = check_rows(rows_f, n_shards, filter->n_rows, "bsi_distinct filter")) return rc;
   if (upper == 0) return FBK_OK;
   if (upper >= (1ull << 31)) return fail(FBK_E_INVALID, "bsi_distinct: more than 2^31 values in one call (split the shard list)");
-  DevBuf dvals, dsorted, duniq, dcur, dtmp, drows, dfrows, ta, tf, dbase, dcounts;
+  DevBuf dvals, dsorted, dcur, dtmp, drows, dfrows, ta, tf, dbase, dcounts;
   HIP_TRY(dvals.alloc(ctx, upper * 8));
   HIP_TRY(dcur.alloc(ctx, 32));  // [0] the running total of values (k_bsi_cell_scan's carry), [1] the number of distinct values, [2] (uint32) the count-mismatch flag
   HIP_TRY(hipMemsetAsync(dcur.p, 0, 32, ctx->stream));
@@ -1804,10 +1798,27 @@ int32_t fbk_bsi_distinct(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* b
   HIP_TRY(hipcub::DeviceRadixSort::SortKeys(dtmp.p, tb, dvals.as<long long>(), dsorted.as<long long>(), int(n_emit), 0, 64, ctx->stream));
   tb = std::max(t1, t2);
   HIP_TRY(hipcub::DeviceSelect::Unique(dtmp.p, tb, dsorted.as<long long>(), duniq.as<long long>(), d_nu, int(n_emit), ctx->stream));
-  u64 n_unique = 0;
   HIP_TRY(hipMemcpyAsync(&n_unique, d_nu, 8, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return FBK_OK;
+}
+
+int32_t fbk_bsi_distinct(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
+                         uint32_t bit_depth, const fbk_batch* filter, const uint32_t* rows_f, int64_t* out_values,
+                         uint64_t cap, uint64_t* out_n) try {
+  FBK_ENTER(ctx);
+  if (!ctx || !batch || !out_n || (n_shards && !base_rows) || (filter && n_shards && !rows_f) || (cap && !out_values))
+    return fail(FBK_E_INVALID, "NULL argument");
+  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  *out_n = 0;
+  if (n_shards == 0) return FBK_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+  DevBuf duniq;
+  u64 n_unique = 0;
+  if (int32_t rc = bsi_distinct_device(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f, duniq, n_unique)) return rc;
   *out_n = n_unique;
+  if (n_unique == 0) return FBK_OK;
   if (n_unique > cap) return fail(FBK_E_CAPACITY, "bsi_distinct: " + std::to_string(n_unique) + " distinct values, buffer holds " + std::to_string(cap));
   HIP_TRY(hipMemcpyAsync(out_values, duniq.p, n_unique * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));

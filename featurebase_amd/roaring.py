@@ -657,6 +657,18 @@ class Context:
         del keep
         return Query(self, h.value, "count_matrix_sum", (n_shards, n_a, n_b))
 
+    def count_matrix_distinct(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, bit_depth: int,
+                              filt: Optional[Batch] = None, rows_f=None) -> Tuple[np.ndarray, np.ndarray]:
+        """GroupBy(..., aggregate=Count(Distinct(field))) of the last two levels: for every pair (i, j) the number of distinct
+        stored values over A_i ∩ B_j ∩ filt ∩ exists, taken over all the shards together, and the number of such columns
+        (b = None: the one-field form, one column).  Arguments as count_matrix_sum.  Returns (distinct, counts), both uint64
+        [n_a, n_b]."""
+        args, keep, n_shards, n_a, n_b = self._msum_args(a, rows_a, b, rows_b, bsi, base_rows, filt, rows_f)
+        distinct, counts = np.zeros((n_a, n_b), dtype=np.uint64), np.zeros((n_a, n_b), dtype=np.uint64)
+        L.check(self.lib.fbk_count_matrix_distinct(*args, bit_depth, n_shards, distinct.ctypes.data, counts.ctypes.data))
+        del keep
+        return distinct, counts
+
     # -- prepared (launch-only) forms of the query-level calls -------------------------------
     def prepare_count_matrix(self, a: Batch, rows_a, b: Batch, rows_b, filt: Optional[Batch] = None, rows_f=None, keep_per_shard: bool = False) -> Query:
         ra = np.ascontiguousarray(rows_a, dtype=np.uint32)

@@ -57,7 +57,8 @@ extern "C" {
 /* ABI history.
  *   6 (round 6): + fbk_comm_unique_id / fbk_comm_init / fbk_comm_all_reduce_u64 / fbk_comm_fence / fbk_comm_close (the
  *      one-process-per-GPU exchange issued by the library itself).  fbk_batch_compact refuses a batch of another context;
- *      fbk_group_topn refuses members whose topn_semantics differ.
+ *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
+ *      fbk_count_matrix_distinct.
  *   5 (round 5): + fbk_topn_partials, options topn_semantics, matrix_shadow_arena_x.  CHANGED: fbk_topn / fbk_query_topn /
  *      fbk_group_topn with 0 < n < n_a return the reference's two-pass answer by default (topn_semantics = 1; = 0 restores
  *      round 4's exact top n of fbk_topn; round 4's per-member candidate rule of fbk_group_topn is gone — it was neither);
@@ -540,6 +541,31 @@ int32_t fbk_query_count_matrix_sum(fbk_ctx* ctx, const fbk_batch* a, const uint3
                                    const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
                                    const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
                                    fbk_query** out_query);
+
+/* ---- GroupBy with aggregate=Count(Distinct(field=v)) -------------------------------------------
+ * For every pair (i, j), over ALL the shards given together (X_s = A.rows_a[s*n_a+i] ∩ B.rows_b[s*n_b+j] ∩ F.rows_f[s] ∩ exists):
+ *   out_distinct[i*n_b+j] = |{ value(c) : c in X_s, any s }|, value = sign ? -magnitude : magnitude (int64 wrap-around, as
+ *                           fbk_bsi_distinct: a set sign bit with magnitude 0 is the value 0); a union of value sets over the
+ *                           shards, not a sum of per-shard counts
+ *   out_counts[i*n_b+j]   = Σ_s |X_s| (may be NULL)
+ * i.e. fbk_bsi_distinct's *out_n over the filter A_i ∩ B_j ∩ F, for all pairs at once: executor.go's Count(Distinct(Intersect(
+ * group rows, filter))) per result group (:3338-3386).  Base is not needed (adding it is a bijection).  Sign and plane bits
+ * outside exists are ignored.  Arguments as fbk_count_matrix_sum: b == NULL is the one-field form (n_b must be 1),
+ * filter == NULL no filter, bit_depth 0..64, n_a, n_b <= 4096; fewer than 2^31 values of exists ∩ F per call; an exists row
+ * whose stored cardinality is wrong gives FBK_E_INVALID.
+ * Device scratch is bounded: the distinct values (fbk_bsi_distinct's buffers, 24 bytes per value of exists ∩ F), then a
+ * presence tile of at most 2^27 bytes: with wb = ceil(n_b / 64), m64 = the number of distinct values rounded up to 64 and
+ * row = 8 * wb * m64, one tile if n_a * row <= 2^27; else, if 64 * row <= 2^27, tiles of floor(2^27 / row) rounded down to a
+ * multiple of 64 A rows; else tiles of min(n_a, 64) A rows x floor(2^27 / (8 * wb * min(n_a, 64))) rounded down to a multiple
+ * of 64 values.  Every tile reads the operands once more.  Rows of batches that are not dense are densified a chunk of shards
+ * at a time: most = max(1, min(n_shards, 2^30 / per_shard)) with per_shard = 2^17 * (n_a if A is not dense, n_b if B is not,
+ * 1 if the filter is not, bit_depth + 2 if the BSI batch is not); chunk = ceil(n_shards / ceil(n_shards / most)); with more
+ * than one chunk every tile densifies them again.  out_counts adds fbk_count_matrix_sum's count pass (its chunk arithmetic
+ * at bit_depth 0). */
+int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
+                                  const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
+                                  const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
+                                  uint64_t* out_distinct, uint64_t* out_counts);
 
 /* ---- BSI (bit-sliced integers) ----------------------------------------------------------------
  * A BSI fragment of shard s occupies bit_depth+2 consecutive rows of `batch` starting at

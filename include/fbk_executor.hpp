@@ -509,11 +509,42 @@ class Executor {
     std::unique_ptr<RowSet> prefix;  // filter ∩ rows of the fields before the last two
     if (filter) prefix.reset(new RowSet(eval(*filter)));
     std::vector<FieldRow> group;
-    group_by_rec(fields, 0, prefix.get(), agg_field, limit, group, out);
+    GroupAgg agg;
+    agg.sum_field = agg_field;
+    group_by_rec(fields, 0, prefix.get(), agg, limit, group, out);
+    return out;
+  }
+
+  // GroupBy(Rows(f0), Rows(f1), ..., filter, aggregate=Count(Distinct(distinct_filter, field=distinct_field))): the groups of
+  // GroupBy (Count = |group ∩ filter|, Count == 0 skipped, odometer order, limit), Agg = the number of distinct values of the
+  // int field over group ∩ filter ∩ distinct_filter (0 when the group has none) — executor.go:3338-3386.  The last one or two
+  // levels take one fbk_count_matrix_distinct call per block of rows.  Int fields only.
+  std::vector<GroupCount> GroupByCountDistinct(const std::vector<std::string>& fields, const Call* filter, const std::string& distinct_field,
+                                               const Call* distinct_filter = nullptr, uint64_t limit = 0) {
+    if (fields.empty()) throw Error(FBK_E_INVALID, "need at least one child call");  // executor.go:3927
+    if (!idx_.ints_.count(distinct_field))
+      throw Error(FBK_E_INVALID, "GroupBy aggregate=Count(Distinct(field=" + distinct_field + ")): " +
+                                     (idx_.sets_.count(distinct_field) ? "set fields are not supported, only int fields" : "no such int field"));
+    Scope sc(*this, {filter, distinct_filter});
+    std::vector<GroupCount> out;
+    if (shards().empty()) return out;
+    std::unique_ptr<RowSet> prefix, dfilt;
+    if (filter) prefix.reset(new RowSet(eval(*filter)));
+    if (distinct_filter) dfilt.reset(new RowSet(eval(*distinct_filter)));
+    std::vector<FieldRow> group;
+    GroupAgg agg;
+    agg.distinct_field = distinct_field;
+    agg.distinct_filter = dfilt.get();
+    group_by_rec(fields, 0, prefix.get(), agg, limit, group, out);
     return out;
   }
 
  private:
+  struct GroupAgg {
+    std::string sum_field;                  // aggregate=Sum(field)
+    std::string distinct_field;             // aggregate=Count(Distinct(X, field))
+    const RowSet* distinct_filter = nullptr;  // X (nullptr: none)
+  };
   // ---- evaluation of bitmap calls ----
   RowSet leaf_row(const std::string& field, uint64_t row) {
     const Index::SetField& f = idx_.sets_.at(field);
@@ -703,6 +734,13 @@ class Executor {
   // rows (the call's limit per side; fbk_count / fbk_count_matrix take up to 2^22 rows against one).  counts[i * nb + j] =
   // columns WITH a value (the group's Count), sums + count * Base = its Agg (executeSumCountShard per group, executor.go:2155-2216).
   static constexpr size_t kSumBlock = 4096;
+  // the rows [k0, k0 + bk) of every shard of a [n][nk] row list
+  static std::vector<uint32_t> row_block(const std::vector<uint32_t>& rows, size_t n, size_t nk, size_t k0, size_t bk) {
+    if (k0 == 0 && bk == nk) return rows;
+    std::vector<uint32_t> out(n * bk);
+    for (size_t s = 0; s < n; ++s) std::copy(rows.begin() + s * nk + k0, rows.begin() + s * nk + k0 + bk, out.begin() + s * bk);
+    return out;
+  }
   void sum_matrix(const std::string& agg_field, const Index::SetField& fa, const std::vector<uint32_t>& rows_a, const Index::SetField* fb,
                   const std::vector<uint32_t>* rows_b, const RowSet* prefix, std::vector<int64_t>& agg, std::vector<uint64_t>& counts) {
     const Index::IntField& f = idx_.ints_.at(agg_field);
@@ -710,18 +748,11 @@ class Executor {
     const size_t n = base.size(), na = fa.row_ids.size(), nb = fb ? fb->row_ids.size() : 1;
     agg.assign(na * nb, 0);
     counts.assign(na * nb, 0);
-    // the rows [k0, k0 + bk) of every shard of a [n][nk] row list
-    auto block = [n](const std::vector<uint32_t>& rows, size_t nk, size_t k0, size_t bk) {
-      if (k0 == 0 && bk == nk) return rows;
-      std::vector<uint32_t> out(n * bk);
-      for (size_t s = 0; s < n; ++s) std::copy(rows.begin() + s * nk + k0, rows.begin() + s * nk + k0 + bk, out.begin() + s * bk);
-      return out;
-    };
     for (size_t i0 = 0; i0 < na; i0 += kSumBlock)
       for (size_t j0 = 0; j0 < nb; j0 += kSumBlock) {
         const size_t bi = std::min(kSumBlock, na - i0), bj = std::min(kSumBlock, nb - j0);
-        const std::vector<uint32_t> ra = block(rows_a, na, i0, bi);
-        const std::vector<uint32_t> rb = fb ? block(*rows_b, nb, j0, bj) : std::vector<uint32_t>();
+        const std::vector<uint32_t> ra = row_block(rows_a, n, na, i0, bi);
+        const std::vector<uint32_t> rb = fb ? row_block(*rows_b, n, nb, j0, bj) : std::vector<uint32_t>();
         std::vector<int64_t> sums(bi * bj);
         std::vector<uint64_t> cnt(bi * bj);
         check(fbk_count_matrix_sum(idx_.ctx_, fa.batch, ra.data(), uint32_t(bi), fb ? fb->batch : nullptr, fb ? rb.data() : nullptr, uint32_t(bj),
@@ -735,10 +766,38 @@ class Executor {
           }
       }
   }
+  // aggregate=Count(Distinct(X, field)) of the last level (fb == nullptr) or the last two levels: fbk_count_matrix_distinct with
+  // prefix ∩ X as the filter, in blocks of kSumBlock x kSumBlock rows as sum_matrix.  distinct[i * nb + j] = the group's Agg.
+  void distinct_matrix(const GroupAgg& agg, const Index::SetField& fa, const std::vector<uint32_t>& rows_a, const Index::SetField* fb,
+                       const std::vector<uint32_t>* rows_b, const RowSet* prefix, std::vector<int64_t>& distinct) {
+    const Index::IntField& f = idx_.ints_.at(agg.distinct_field);
+    std::vector<uint32_t> base = base_rows(f);
+    const size_t n = base.size(), na = fa.row_ids.size(), nb = fb ? fb->row_ids.size() : 1;
+    std::unique_ptr<RowSet> both;
+    const RowSet* filt = prefix ? prefix : agg.distinct_filter;
+    if (prefix && agg.distinct_filter) {
+      both.reset(new RowSet(setop(FBK_OP_AND, *prefix, *agg.distinct_filter)));
+      filt = both.get();
+    }
+    distinct.assign(na * nb, 0);
+    for (size_t i0 = 0; i0 < na; i0 += kSumBlock)
+      for (size_t j0 = 0; j0 < nb; j0 += kSumBlock) {
+        const size_t bi = std::min(kSumBlock, na - i0), bj = std::min(kSumBlock, nb - j0);
+        const std::vector<uint32_t> ra = row_block(rows_a, n, na, i0, bi);
+        const std::vector<uint32_t> rb = fb ? row_block(*rows_b, n, nb, j0, bj) : std::vector<uint32_t>();
+        std::vector<uint64_t> d(bi * bj);
+        check(fbk_count_matrix_distinct(idx_.ctx_, fa.batch, ra.data(), uint32_t(bi), fb ? fb->batch : nullptr, fb ? rb.data() : nullptr, uint32_t(bj),
+                                        filt ? filt->batch() : nullptr, filt ? filt->rows().data() : nullptr, f.batch, base.data(), f.bit_depth,
+                                        uint32_t(n), d.data(), nullptr));
+        for (size_t i = 0; i < bi; ++i)
+          for (size_t j = 0; j < bj; ++j) distinct[(i0 + i) * nb + j0 + j] = int64_t(d[i * bj + j]);
+      }
+  }
   // fields[level..]: the last two levels are one count-matrix call (one count-matrix-sum call with an aggregate); earlier levels
   // materialise prefix ∩ row (gbi.rows[i].row.Intersect(gbi.rows[i-1].row), executor.go:8829-8834)
-  bool group_by_rec(const std::vector<std::string>& fields, size_t level, const RowSet* prefix, const std::string& agg_field, uint64_t limit,
+  bool group_by_rec(const std::vector<std::string>& fields, size_t level, const RowSet* prefix, const GroupAgg& ag, uint64_t limit,
                     std::vector<FieldRow>& group, std::vector<GroupCount>& out) {
+    const std::string& agg_field = ag.sum_field;
     const size_t n = shards().size();
     const Index::SetField& fa = idx_.sets_.at(fields[level]);
     const size_t na = fa.row_ids.size();
@@ -759,6 +818,7 @@ class Executor {
         for (size_t s = 0; s < n; ++s)
           for (size_t i = 0; i < na; ++i) tot[i] += c[s * na + i];
       }
+      if (!ag.distinct_field.empty()) distinct_matrix(ag, fa, rows_a, nullptr, nullptr, prefix, agg);
       for (size_t i = 0; i < na; ++i) {
         if (!tot[i]) continue;
         group.push_back({fields[level], fa.row_ids[i]});
@@ -775,11 +835,24 @@ class Executor {
       std::vector<uint32_t> rows_b = field_rows(fb);
       std::vector<uint64_t> tot(na * nb, 0);
       std::vector<int64_t> agg(na * nb, 0);
-      if (!agg_field.empty())
+      if (!agg_field.empty()) {
         sum_matrix(agg_field, fa, rows_a, &fb, &rows_b, prefix, agg, tot);
-      else
+      } else if (!ag.distinct_field.empty()) {
+        // Count: the count matrix in blocks of kSumBlock x kSumBlock rows (its limit per side); Agg: the distinct matrix
+        for (size_t i0 = 0; i0 < na; i0 += kSumBlock)
+          for (size_t j0 = 0; j0 < nb; j0 += kSumBlock) {
+            const size_t bi = std::min(kSumBlock, na - i0), bj = std::min(kSumBlock, nb - j0);
+            const std::vector<uint32_t> ra = row_block(rows_a, n, na, i0, bi), rb = row_block(rows_b, n, nb, j0, bj);
+            std::vector<uint64_t> c(bi * bj);
+            check(fbk_count_matrix(idx_.ctx_, fa.batch, ra.data(), uint32_t(bi), fb.batch, rb.data(), uint32_t(bj), prefix ? prefix->batch() : nullptr,
+                                   prefix ? prefix->rows().data() : nullptr, uint32_t(n), c.data(), nullptr));
+            for (size_t i = 0; i < bi; ++i) std::copy(c.begin() + i * bj, c.begin() + (i + 1) * bj, tot.begin() + (i0 + i) * nb + j0);
+          }
+        distinct_matrix(ag, fa, rows_a, &fb, &rows_b, prefix, agg);
+      } else {
         check(fbk_count_matrix(idx_.ctx_, fa.batch, rows_a.data(), uint32_t(na), fb.batch, rows_b.data(), uint32_t(nb), prefix ? prefix->batch() : nullptr,
                                prefix ? prefix->rows().data() : nullptr, uint32_t(n), tot.data(), nullptr));
+      }
       for (size_t i = 0; i < na; ++i)
         for (size_t j = 0; j < nb; ++j) {
           if (!tot[i * nb + j]) continue;
@@ -798,9 +871,9 @@ class Executor {
       bool go;
       if (prefix) {
         RowSet p = setop(FBK_OP_AND, r, *prefix);
-        go = count_rows(p) == 0 ? true : group_by_rec(fields, level + 1, &p, agg_field, limit, group, out);
+        go = count_rows(p) == 0 ? true : group_by_rec(fields, level + 1, &p, ag, limit, group, out);
       } else {
-        go = group_by_rec(fields, level + 1, &r, agg_field, limit, group, out);
+        go = group_by_rec(fields, level + 1, &r, ag, limit, group, out);
       }
       group.pop_back();
       if (!go) return false;
