@@ -126,6 +126,12 @@ SIGNATURES = {
     "fbk_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "fbk_query_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_count_matrix_distinct": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "fbk_extract_open": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vpp, _u64p]),
+    "fbk_extract_span": (C.c_int32, [_vp, _vp, _u32p, _u32p]),
+    "fbk_extract_columns": (C.c_int32, [_vp, _vp, _vp]),
+    "fbk_extract_bsi": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "fbk_extract_rows": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p]),
+    "fbk_extract_free": (C.c_int32, [_vp, _vp]),
     "fbk_bsi_min": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fbk_bsi_max": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fbk_bsi_distinct": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),

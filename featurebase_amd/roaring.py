@@ -254,6 +254,59 @@ class Query:
             self.h = C.c_void_p(None)
 
 
+class Extract:
+    """The selected columns of Extract(filter, ...) (fbk_extract_*): fixed once by Context.extract, then one call per field.
+    Keep the filter batch alive while the handle is, and close() it before the context."""
+
+    def __init__(self, ctx: "Context", handle: int, n: int, n_shards: int, keep):
+        self.ctx, self.h, self.n, self.n_shards, self._keep = ctx, C.c_void_p(handle), n, n_shards, keep
+
+    def span(self) -> Tuple[int, int]:
+        """(first, count): the shards (positions in the call's shard list) that hold a selected column"""
+        a, b = C.c_uint32(), C.c_uint32()
+        L.check(self.ctx.lib.fbk_extract_span(self.ctx.h, self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def columns(self) -> np.ndarray:
+        out = np.zeros(self.n, dtype=np.uint64)
+        L.check(self.ctx.lib.fbk_extract_columns(self.ctx.h, self.h, out.ctypes.data))
+        return out
+
+    def bsi(self, batch: Batch, base_rows, bit_depth: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Int field: (values int64[n] — sign applied, Base not added, 0 where absent —, present bool[n])"""
+        base = np.ascontiguousarray(base_rows, dtype=np.uint32)
+        assert base.size == self.n_shards
+        vals, pres = np.zeros(self.n, dtype=np.int64), np.zeros(self.n, dtype=np.uint8)
+        L.check(self.ctx.lib.fbk_extract_bsi(self.ctx.h, self.h, batch.h, base.ctypes.data, bit_depth, vals.ctypes.data, pres.ctypes.data))
+        return vals, pres.astype(bool)
+
+    def rows(self, batch: Batch, rows_a, cap: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Set field, rows_a [n_shards, n_a]: CSR (offsets uint64[n + 1], items uint32[m]): the items of column k are the
+        indices i (ascending) of the rows that hold it.  One retry with the reported size when `cap` items were too few."""
+        ra = np.ascontiguousarray(rows_a, dtype=np.uint32).reshape(self.n_shards, -1)
+        offs, m = np.zeros(self.n + 1, dtype=np.uint64), C.c_uint64()
+        cap = max(self.n, 1) if cap is None else cap
+        for _ in range(2):
+            items = np.zeros(max(cap, 1), dtype=np.uint32)
+            rc = self.ctx.lib.fbk_extract_rows(self.ctx.h, self.h, batch.h, ra.ctypes.data, ra.shape[1], offs.ctypes.data, items.ctypes.data, cap, C.byref(m))
+            if rc != L.FBK_E_CAPACITY:
+                break
+            cap = int(m.value)
+        L.check(rc)
+        return offs, items[: m.value].copy()
+
+    def close(self) -> None:
+        if self.h:
+            L.check(self.ctx.lib.fbk_extract_free(self.ctx.h, self.h))
+            self.h = C.c_void_p(None)
+
+    def __enter__(self) -> "Extract":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
 class Context:
     """One GPU.  Fails loudly when libfbk.so is missing or no gfx950 device is visible."""
 
@@ -622,6 +675,18 @@ class Context:
             )
         )
         return (tot, ps) if per_shard else tot
+
+    # -- Extract -------------------------------------------------------------------------------
+    def extract(self, filt: Batch, rows_f, shard_ids, offset: int = 0, limit: Optional[int] = None) -> Extract:
+        """Extract(Limit(filter, limit=, offset=), ...): the filter's columns (rows_f [n_shards] of `filt`, shard_ids strictly
+        ascending) in ascending order, ranks [offset, offset + limit).  Returns the handle (.n columns) the per-field calls take."""
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32)
+        ids = np.ascontiguousarray(shard_ids, dtype=np.uint64)
+        assert rf.size == ids.size
+        h, n = C.c_void_p(), C.c_uint64()
+        L.check(self.lib.fbk_extract_open(self.h, filt.h, rf.ctypes.data, ids.ctypes.data, rf.size, offset, (1 << 64) - 1 if limit is None else limit,
+                                          C.byref(h), C.byref(n)))
+        return Extract(self, h.value, int(n.value), int(rf.size), filt)
 
     # -- GroupBy with aggregate=Sum ------------------------------------------------------------
     def _msum_args(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, filt: Optional[Batch], rows_f):

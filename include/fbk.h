@@ -58,7 +58,7 @@ extern "C" {
  *   6 (round 6): + fbk_comm_unique_id / fbk_comm_init / fbk_comm_all_reduce_u64 / fbk_comm_fence / fbk_comm_close (the
  *      one-process-per-GPU exchange issued by the library itself).  fbk_batch_compact refuses a batch of another context;
  *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
- *      fbk_count_matrix_distinct.
+ *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free.
  *   5 (round 5): + fbk_topn_partials, options topn_semantics, matrix_shadow_arena_x.  CHANGED: fbk_topn / fbk_query_topn /
  *      fbk_group_topn with 0 < n < n_a return the reference's two-pass answer by default (topn_semantics = 1; = 0 restores
  *      round 4's exact top n of fbk_topn; round 4's per-member candidate rule of fbk_group_topn is gone — it was neither);
@@ -566,6 +566,58 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
                                   const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
                                   const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
                                   uint64_t* out_distinct, uint64_t* out_counts);
+
+/* ---- Extract(filter, Rows(f1), Rows(f2), ...): the records of a column filter -------------------
+ * executeExtract (executor.go:4711-5046), usually under executeLimitCall's Extract(Limit(filter, limit=, offset=), ...)
+ * (:1027-1100).  A handle fixes the selected columns once, then one call per field rotates that field's bits into per-column
+ * results on the device (64 x 64 in-register transposes; a column's output slot is its rank, computed from popcounts).
+ *
+ * fbk_extract_open: the selected columns are the set bits of filter.rows_f[s], s = 0 .. n_shards-1, in the order given
+ * (shard_ids strictly ascending and < 2^44), column = shard_ids[s] * 2^20 + position; of these the ranks [offset, offset + limit)
+ * (limit = UINT64_MAX: no limit; offset + limit may exceed 2^64) — offset, then limit, on the ascending column list.  *out_n = n,
+ * their number.
+ *  - Selection is computed from the filter's WORDS, never from stored cardinalities: a batch whose stored cardinality is wrong
+ *    cannot misplace output.
+ *  - n must be below 2^31, otherwise FBK_E_INVALID (the message says to use a limit).  n == 0 (empty filter, limit == 0,
+ *    offset >= the filter's count, n_shards == 0) is a valid handle whose calls write nothing but out_offsets[0] = 0 and
+ *    *out_n_items = 0.
+ *  - The call synchronises once (it returns n).  It records the span of shards [first, first + count) that hold a selected column
+ *    (fbk_extract_span); the per-field calls never densify or read a shard outside that span, and inside it skip every 1024-column
+ *    unit and every 64-column word without a selected column: Extract(Limit(All(), limit=1000)) over a thousand shards costs a
+ *    few words per row, not the field.
+ *  - Resident in the handle until fbk_extract_free: per shard OF THE SPAN 2^17 bytes (the filter's words with the selected
+ *    columns only — a dense copy, whatever the filter's encoding) + 2^12 bytes (the rank of every 1024-column unit's first
+ *    column), and 8 bytes per shard of the call.  The handle does not read the filter batch after open, but it belongs to the
+ *    query that owns that batch: keep the filter batch alive until the handle is freed, and free every handle before fbk_close.
+ *  - The handle belongs to the context that opened it (another context: FBK_E_INVALID) and every call takes that context's lock
+ *    and stream; its resident state is its own, not the context's scratch: several handles may be alive and used alternately.
+ *  - Filter, BSI and A batches may be dense or encoded.  Rows of a batch that is not dense are densified a chunk at a time into at
+ *    most 2^28 bytes of scratch: with R the rows densified per shard (filter: 1; fbk_extract_bsi: bit_depth + 2;
+ *    fbk_extract_rows: n_a) and per_shard = 2^17 * R: if per_shard <= 2^28, most = max(1, min(shards, 2^28 / per_shard)) and
+ *    chunk = ceil(shards / ceil(shards / most)) shards per launch with all their rows; else one shard per launch in blocks of
+ *    2^28 / 2^17 = 2048 rows.  `shards` is n_shards for fbk_extract_open (both of its passes) and the span's count for the
+ *    per-field calls.  Results do not depend on the chunking or on the grid size.
+ *
+ * fbk_extract_columns: out_columns[k], k < n: the selected columns, ascending.
+ * fbk_extract_bsi (int field, layout of fbk_bsi_sum, base_rows [n_shards] as given to open, bit_depth 0..64):
+ *   out_present[k] = 1 and out_values[k] = sign ? -magnitude : magnitude (Base NOT added, int64 wrap-around, a set sign bit over
+ *   magnitude 0 is 0 — as fbk_bsi_distinct) when column k is in exists; else 0 and 0.  Sign and plane bits outside exists are
+ *   ignored (executor.go:5007, :5016 intersect with exists).  Every element of both arrays is written.
+ * fbk_extract_rows (set / mutex / bool field, rows_a = [n_shards][n_a] as fbk_count_matrix's, n_a <= 4096): CSR over the n columns:
+ *   the items of column k = out_items[out_offsets[k] .. out_offsets[k+1]) = the indices i (0 .. n_a-1, ascending) with the column
+ *   in A.rows_a[s*n_a+i].  *out_n_items is always set; cap too small -> FBK_E_CAPACITY, out_offsets [n+1] still complete,
+ *   out_items untouched (the fbk_bsi_distinct convention).  Fields of more than 4096 rows take one call per block of rows.
+ * fbk_extract_free: NULL handle is a no-op. */
+typedef struct fbk_extract fbk_extract;
+int32_t fbk_extract_open(fbk_ctx* ctx, const fbk_batch* filter, const uint32_t* rows_f, const uint64_t* shard_ids, uint32_t n_shards,
+                         uint64_t offset, uint64_t limit, fbk_extract** out, uint64_t* out_n);
+int32_t fbk_extract_span(fbk_ctx* ctx, const fbk_extract* h, uint32_t* out_first, uint32_t* out_count);
+int32_t fbk_extract_columns(fbk_ctx* ctx, fbk_extract* h, uint64_t* out_columns);
+int32_t fbk_extract_bsi(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth,
+                        int64_t* out_values, uint8_t* out_present);
+int32_t fbk_extract_rows(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, uint64_t* out_offsets,
+                         uint32_t* out_items, uint64_t cap, uint64_t* out_n_items);
+int32_t fbk_extract_free(fbk_ctx* ctx, fbk_extract* h);
 
 /* ---- BSI (bit-sliced integers) ----------------------------------------------------------------
  * A BSI fragment of shard s occupies bit_depth+2 consecutive rows of `batch` starting at

@@ -10,6 +10,7 @@
 //   executeTopK (doTopK + PivotDescending)       executor.go:2357-2412, 2705-2746, bsi.go:18-62
 //   executeTopN (counts; the rank cache is not mirrored)   executor.go:2776-2868
 //   executeGroupBy (groupByIterator odometer)    executor.go:3918-3990, 8617-8934
+//   executeExtract (+ executeLimitCall)          executor.go:4711-5046, 1027-1100
 // Every shard of a query is evaluated in ONE device call per operator (the reference maps a
 // closure over shards, executor.go:6449); the cross-shard reduce is the same associative
 // arithmetic (sum of counts, ValCount.Add/Smaller/Larger, concatenation of row segments).
@@ -19,6 +20,7 @@
 #include <algorithm>
 #include <map>
 #include <memory>
+#include <optional>
 #include <set>
 #include <string>
 #include <vector>
@@ -54,6 +56,16 @@ struct ValCount {  // executor.go:8380; integer fields only
     return {Val, Count + (Val == o.Val ? o.Count : 0)};
   }
   bool operator==(const ValCount& o) const { return Val == o.Val && Count == o.Count; }
+};
+
+// Extract's result (executor.go ExtractedIDMatrix / ExtractedIDColumn): per column one entry per field, null (no value) or a list
+struct ExtractedIDColumn {
+  uint64_t ColumnID = 0;
+  std::vector<std::optional<std::vector<uint64_t>>> Rows;
+};
+struct ExtractedIDMatrix {
+  std::vector<std::string> Fields;
+  std::vector<ExtractedIDColumn> Columns;
 };
 
 // A PQL bitmap call (the subset on the hot path).
@@ -536,6 +548,72 @@ class Executor {
     agg.distinct_field = distinct_field;
     agg.distinct_filter = dfilt.get();
     group_by_rec(fields, 0, prefix.get(), agg, limit, group, out);
+    return out;
+  }
+
+  // ---- Extract --------------------------------------------------------------------------------
+  // Extract(Limit(filter, limit=, offset=), Rows(f0), Rows(f1), ...) (executeExtract, executor.go:4711-5046; executeLimitCall,
+  // :1027-1100): the filter's columns in ascending order, offset then limit, and per column one entry per field:
+  //   int field   [value + Base] as uint64(int64) (:5023), or null when the column has no value;
+  //   set field   the row ids ascending; a column with no bit gets an EMPTY, non-null list (the reference's branch for set fields
+  //               without existence tracking, :4836-4842 — this mirror has no per-field existence view).
+  // One fbk_extract_open for the filter, then one fbk_extract_bsi per int field and one fbk_extract_rows per block of kSumBlock
+  // rows of a set field (the per-column lists concatenated in block order, as GroupByCountDistinct blocks wide fields).
+  ExtractedIDMatrix Extract(const Call& filter, const std::vector<std::string>& fields, uint64_t limit = UINT64_MAX, uint64_t offset = 0) {
+    for (const std::string& name : fields)
+      if (!idx_.sets_.count(name) && !idx_.ints_.count(name)) throw Error(FBK_E_INVALID, "field not found: " + name);  // ErrFieldNotFound
+    Scope sc(*this, {&filter});
+    ExtractedIDMatrix out;
+    out.Fields = fields;
+    const size_t n = shards().size();
+    if (n == 0) return out;
+    RowSet fr = eval(filter);
+    struct Handle {
+      fbk_ctx* ctx;
+      fbk_extract* h = nullptr;
+      ~Handle() { fbk_extract_free(ctx, h); }
+    } hd{idx_.ctx_};
+    uint64_t cnt = 0;
+    check(fbk_extract_open(idx_.ctx_, fr.batch(), fr.rows().data(), shards().data(), uint32_t(n), offset, limit, &hd.h, &cnt));
+    std::vector<uint64_t> cols(cnt);
+    check(fbk_extract_columns(idx_.ctx_, hd.h, cols.data()));
+    out.Columns.resize(cnt);
+    for (uint64_t k = 0; k < cnt; ++k) {
+      out.Columns[k].ColumnID = cols[k];
+      out.Columns[k].Rows.resize(fields.size());
+    }
+    for (size_t fi = 0; fi < fields.size(); ++fi) {
+      auto it = idx_.ints_.find(fields[fi]);
+      if (it != idx_.ints_.end()) {
+        const Index::IntField& f = it->second;
+        const std::vector<uint32_t> base = base_rows(f);
+        std::vector<int64_t> vals(cnt);
+        std::vector<uint8_t> pres(cnt);
+        check(fbk_extract_bsi(idx_.ctx_, hd.h, f.batch, base.data(), f.bit_depth, vals.data(), pres.data()));
+        for (uint64_t k = 0; k < cnt; ++k)
+          if (pres[k]) out.Columns[k].Rows[fi] = std::vector<uint64_t>{uint64_t(vals[k] + f.base)};
+        continue;
+      }
+      const Index::SetField& f = idx_.sets_.at(fields[fi]);
+      for (uint64_t k = 0; k < cnt; ++k) out.Columns[k].Rows[fi] = std::vector<uint64_t>();
+      const size_t nr = f.row_ids.size();
+      const std::vector<uint32_t> rows_a = nr ? field_rows(f) : std::vector<uint32_t>();
+      std::vector<uint64_t> offs(cnt + 1);
+      std::vector<uint32_t> items;
+      for (size_t i0 = 0; i0 < nr; i0 += kSumBlock) {
+        const size_t bi = std::min(kSumBlock, nr - i0);
+        const std::vector<uint32_t> ra = row_block(rows_a, n, nr, i0, bi);
+        uint64_t m = 0;
+        int32_t rc = fbk_extract_rows(idx_.ctx_, hd.h, f.batch, ra.data(), uint32_t(bi), offs.data(), items.data(), items.size(), &m);
+        if (rc == FBK_E_CAPACITY) {
+          items.resize(m);
+          rc = fbk_extract_rows(idx_.ctx_, hd.h, f.batch, ra.data(), uint32_t(bi), offs.data(), items.data(), items.size(), &m);
+        }
+        check(rc);
+        for (uint64_t k = 0; k < cnt; ++k)
+          for (uint64_t p = offs[k]; p < offs[k + 1]; ++p) out.Columns[k].Rows[fi]->push_back(f.row_ids[i0 + items[p]]);
+      }
+    }
     return out;
   }
 
