@@ -35,6 +35,7 @@
 #include "fbk_matrix_sum.hip.h"
 #include "fbk_matrix_distinct.hip.h"
 #include "fbk_extract.hip.h"
+#include "fbk_sort.hip.h"
 #include "fbk_wire_kernels.hip.h"
 
 using fbk::Slot;
@@ -1937,6 +1938,7 @@ int32_t fbk_setop(fbk_ctx* ctx, int32_t op, const fbk_batch* a, const uint32_t* 
 #include "fbk_matrix_sum_api.inc"
 #include "fbk_matrix_distinct_api.inc"
 #include "fbk_extract_api.inc"
+#include "fbk_sort_api.inc"
 #include "fbk_prepared_api.inc"
 #include "fbk_wire_api.inc"
 #include "fbk_cache_api.inc"

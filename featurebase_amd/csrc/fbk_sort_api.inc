@@ -1,0 +1,255 @@
+// fbk_sort_api.inc — fbk_bsi_sort (Sort() by an int field) and fbk_extract_open_columns (an extract handle from a column list):
+// fbk_sort.hip.h.  Included by fbk.hip after fbk_extract_api.inc.
+//
+// fbk_bsi_sort walks the shards a few times (a radix-select pass per 11 key bits, a count pass, a collect pass).  A walk densifies
+// what is not dense a chunk of shards at a time, by fbk_extract_*'s rule with R = (field encoded ? bit_depth + 2 : 0) +
+// (filter encoded ? 1 : 0) rows per shard: the filter's rows first, then the field's.  Device scratch (fbk.h documents it):
+//   2^14 + 2^23 (histogram, the blocks' partial histograms) + 2^15 per shard (counts and prefixes of its 1024 units, key < T and
+//   key == T) + the densify chunk (<= 2^28) + 16 K (candidates) + 16 n_less + the radix sort's temporary storage (sorted pairs)
+//   + 16 n (the records) + the row lists.
+
+namespace {
+
+struct SortWalk {
+  const uint8_t* arenaS;
+  const uint32_t* rowsS;
+  const uint8_t* arenaF;
+  const uint32_t* rowsF;
+  uint32_t ns, abs0;
+};
+
+}  // namespace
+
+extern "C" {
+
+int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, const fbk_batch* filter, const uint32_t* rows_f,
+                     const uint64_t* shard_ids, uint32_t n_shards, uint32_t flags, uint64_t offset, uint64_t limit, uint64_t* out_columns,
+                     int64_t* out_values, uint64_t cap, uint64_t* out_n, uint64_t* out_total) try {
+  FBK_ENTER(ctx);
+  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (!out_n || (n_shards && (!base_rows || !shard_ids)) || (cap && (!out_columns || !out_values))) return fail(FBK_E_INVALID, "NULL argument");
+  *out_n = 0;
+  if (out_total) *out_total = 0;
+  if (flags & ~uint32_t(FBK_SORT_DESC | FBK_SORT_KEEP_ZERO)) return fail(FBK_E_INVALID, "sort: unknown flag");
+  for (uint32_t s = 0; s < n_shards; ++s) {
+    if (shard_ids[s] >= (1ull << 44)) return fail(FBK_E_INVALID, "sort: shard id >= 2^44 (column ids are shard * 2^20 + position)");
+    if (s && shard_ids[s] <= shard_ids[s - 1]) return fail(FBK_E_INVALID, "sort: shard_ids must be strictly ascending");
+  }
+  if (n_shards > (1u << 20)) return fail(FBK_E_INVALID, "sort: at most 2^20 shards per call");
+  if (!ctx || !bsi || (filter && n_shards && !rows_f)) return fail(FBK_E_INVALID, "NULL argument");
+  const uint64_t rps = uint64_t(bit_depth) + 2;
+  for (uint32_t s = 0; s < n_shards; ++s)
+    if (uint64_t(base_rows[s]) + rps > bsi->n_rows) return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (filter)
+    if (int32_t rc = check_rows(rows_f, n_shards, filter->n_rows, "sort filter")) return rc;
+  if (n_shards == 0) return FBK_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+
+  // the key (fbk_sort.hip.h)
+  fbk::SortKey sk{};
+  const bool wide = bit_depth >= 63;
+  const uint32_t nbits = wide ? 64 : bit_depth + 1;
+  sk.flip = wide ? 1ull << 63 : 0, sk.bias = wide ? 0 : 1ull << bit_depth;
+  sk.desc = (flags & FBK_SORT_DESC) ? (nbits == 64 ? ~0ull : (1ull << nbits) - 1) : 0;
+  sk.keep_zero = (flags & FBK_SORT_KEEP_ZERO) ? 1 : 0;
+  const uint32_t passes = (nbits + fbk::kSortDigitBits - 1) / fbk::kSortDigitBits;
+
+  // row lists and the densify chunk
+  const bool ds = !bsi->dense, df = filter && !filter->dense;
+  const uint32_t R = uint32_t((ds ? rps : 0) + (df ? 1 : 0));
+  const ExtractChunks ck = R ? extract_chunks(n_shards, R) : ExtractChunks{n_shards, 0};
+  const uint32_t foff = df ? ck.shards : 0;  // the field's rows follow the chunk's filter rows
+  std::vector<uint32_t> all(ds ? uint64_t(n_shards) * rps : 0), ibase(ds ? ck.shards : 0), fidx(df ? ck.shards : 0);
+  for (uint32_t s = 0; s < n_shards && ds; ++s)
+    for (uint64_t r = 0; r < rps; ++r) all[uint64_t(s) * rps + r] = uint32_t(base_rows[s] + r);
+  for (uint64_t i = 0; i < ibase.size(); ++i) ibase[i] = uint32_t(foff + i * rps);
+  for (uint64_t i = 0; i < fidx.size(); ++i) fidx[i] = uint32_t(i);
+  DevBuf rows, dense, ids, hist, part, n_lt, n_eq, p_lt, p_eq, keys, cols, skeys, scols, tmp, ocols, ovals;
+  const uint32_t* d[5];
+  if (int32_t rc = upload_rows_multi(ctx, {{base_rows, n_shards, UINT32_MAX}, {all.data(), all.size(), UINT32_MAX}, {ibase.data(), ibase.size(), UINT32_MAX},
+                                           {filter ? rows_f : nullptr, filter ? n_shards : 0, UINT32_MAX}, {fidx.data(), fidx.size(), UINT32_MAX}}, rows, d))
+    return rc;
+  if (R) HIP_TRY(dense.alloc(ctx, uint64_t(ck.shards) * R * kExtractRowBytes));
+  HIP_TRY(ids.alloc(ctx, uint64_t(n_shards) * 8));
+  HIP_TRY(hipMemcpyAsync(ids.p, shard_ids, uint64_t(n_shards) * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hist.alloc(ctx, fbk::kSortBins * 8));
+  HIP_TRY(part.alloc(ctx, uint64_t(fbk::kSortHistBlocks) * fbk::kSortBins * 4));
+  // one walk over the shards: launch(w) per chunk, everything of the chunk dense
+  auto walk = [&](auto&& launch) {
+    for (uint32_t s0 = 0; s0 < n_shards; s0 += ck.shards) {
+      const uint32_t ns = R ? std::min(ck.shards, n_shards - s0) : n_shards;
+      if (df) extract_densify(ctx, filter, d[3] + s0, ns, dense.as<uint8_t>());
+      if (ds) extract_densify(ctx, bsi, d[1] + uint64_t(s0) * rps, uint64_t(ns) * rps, dense.as<uint8_t>() + uint64_t(foff) * kExtractRowBytes);
+      SortWalk w;
+      w.arenaS = ds ? dense.as<uint8_t>() : bsi->d_arena, w.rowsS = ds ? d[2] : d[0] + s0;
+      w.arenaF = !filter ? nullptr : df ? dense.as<uint8_t>() : filter->d_arena, w.rowsF = !filter ? nullptr : df ? d[4] : d[3] + s0;
+      w.ns = ns, w.abs0 = s0;
+      launch(w, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)));
+      if (!R) break;
+    }
+  };
+
+  // radix select: total, then the K-th smallest key T, the columns below it and the ties to take
+  std::vector<uint64_t> hh(fbk::kSortBins);
+  uint64_t total = 0, K = 0, T = 0, n_less = 0, r = 0, want = 0;
+  bool take_all = false;
+  for (uint32_t p = 0; p < passes; ++p) {
+    const uint32_t shift = fbk::kSortDigitBits * (passes - 1 - p);
+    HIP_TRY(hipMemsetAsync(hist.p, 0, fbk::kSortBins * 8, ctx->stream));
+    walk([&](const SortWalk& w, dim3 grid) {
+      const uint32_t nb = std::min(grid.x, fbk::kSortHistBlocks);
+      hipLaunchKernelGGL(fbk::k_sort_hist, dim3(nb), dim3(256), 0, ctx->stream, w.arenaS, w.rowsS, w.arenaF, w.rowsF, w.ns, bit_depth, sk, shift, u64(T),
+                         p ? 1u : 0u, part.as<uint32_t>());
+      hipLaunchKernelGGL(fbk::k_sort_hist_sum, dim3(fbk::kSortBins / 256, 32), dim3(256), 0, ctx->stream, part.as<uint32_t>(), nb, hist.as<u64>());
+    });
+    HIP_TRY(hipGetLastError());
+    {
+      D2H back(ctx);
+      HIP_TRY(back.add(hh.data(), hist.p, fbk::kSortBins * 8));
+      HIP_TRY(back.finish());
+      ctx->h_stage_used = 0;  // (row lists and histogram have left the staging area)
+    }
+    if (p == 0) {
+      for (uint64_t c : hh) total += c;
+      if (out_total) *out_total = total;
+      const uint64_t lo = std::min(offset, total);
+      K = lo + std::min(limit, total - lo);
+      if (K >= (1ull << 31))
+        return fail(FBK_E_INVALID, "sort: " + std::to_string(K) + " records to order (offset + limit, or every column without a limit); one call takes fewer than 2^31: use a limit");
+      *out_n = K - lo;
+      if (*out_n > cap) return fail(FBK_E_CAPACITY, "sort: " + std::to_string(*out_n) + " records, capacity " + std::to_string(cap));
+      if (*out_n == 0) return FBK_OK;
+      want = K;
+      take_all = K == total;
+      if (take_all) break;
+    }
+    uint64_t before = 0;
+    uint32_t b = 0;
+    while (b + 1 < fbk::kSortBins && before + hh[b] < want) before += hh[b++];
+    n_less += before, want -= before, T = (T << fbk::kSortDigitBits) | b;
+  }
+  r = take_all ? 0 : want;
+  if (take_all) n_less = K;
+
+  // ranks of the candidates, then the candidates
+  const uint64_t n_units = uint64_t(n_shards) * fbk::kExtractUnits;
+  HIP_TRY(n_lt.alloc(ctx, (n_units + 1) * 8));
+  HIP_TRY(n_eq.alloc(ctx, (n_units + 1) * 8));
+  HIP_TRY(p_lt.alloc(ctx, (n_units + 1) * 8));
+  HIP_TRY(p_eq.alloc(ctx, (n_units + 1) * 8));
+  HIP_TRY(hipMemsetAsync(n_lt.as<u64>() + n_units, 0, 8, ctx->stream));
+  HIP_TRY(hipMemsetAsync(n_eq.as<u64>() + n_units, 0, 8, ctx->stream));
+  walk([&](const SortWalk& w, dim3 grid) {
+    hipLaunchKernelGGL(fbk::k_sort_count, grid, dim3(256), 0, ctx->stream, w.arenaS, w.rowsS, w.arenaF, w.rowsF, w.ns, w.abs0, bit_depth, sk, u64(T),
+                       take_all ? 1u : 0u, n_lt.as<u64>(), n_eq.as<u64>());
+  });
+  size_t t_scan = 0, t_sort = 0;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t_scan, n_lt.as<u64>(), p_lt.as<u64>(), int(n_units + 1), ctx->stream));
+  if (n_less)
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t_sort, static_cast<const u64*>(nullptr), static_cast<u64*>(nullptr), static_cast<const u64*>(nullptr),
+                                               static_cast<u64*>(nullptr), int(n_less), 0, int(nbits), ctx->stream));
+  HIP_TRY(tmp.alloc(ctx, std::max<size_t>(std::max(t_scan, t_sort), 16)));
+  size_t tb = t_scan;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, n_lt.as<u64>(), p_lt.as<u64>(), int(n_units + 1), ctx->stream));
+  tb = t_scan;
+  HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, n_eq.as<u64>(), p_eq.as<u64>(), int(n_units + 1), ctx->stream));
+  HIP_TRY(keys.alloc(ctx, K * 8));
+  HIP_TRY(cols.alloc(ctx, K * 8));
+  walk([&](const SortWalk& w, dim3 grid) {
+    hipLaunchKernelGGL(fbk::k_sort_collect, grid, dim3(256), 0, ctx->stream, w.arenaS, w.rowsS, w.arenaF, w.rowsF, w.ns, w.abs0, bit_depth, sk, u64(T),
+                       take_all ? 1u : 0u, p_lt.as<u64>(), p_eq.as<u64>(), ids.as<u64>(), u64(n_less), u64(r), keys.as<u64>(), cols.as<u64>());
+  });
+  HIP_TRY(hipGetLastError());
+
+  // order the columns below T (stable: equal keys stay in ascending column order), cut, download
+  const uint64_t n = *out_n, lo = K - n;
+  if (n_less) {
+    HIP_TRY(skeys.alloc(ctx, n_less * 8));
+    HIP_TRY(scols.alloc(ctx, n_less * 8));
+    tb = t_sort;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.as<u64>(), skeys.as<u64>(), cols.as<u64>(), scols.as<u64>(), int(n_less), 0, int(nbits), ctx->stream));
+  }
+  HIP_TRY(ocols.alloc(ctx, n * 8));
+  HIP_TRY(ovals.alloc(ctx, n * 8));
+  hipLaunchKernelGGL(fbk::k_sort_emit, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, skeys.as<u64>(), scols.as<u64>(), keys.as<u64>(),
+                     cols.as<u64>(), u64(n_less), u64(lo), u64(n), sk, ocols.as<u64>(), ovals.as<long long>());
+  HIP_TRY(hipGetLastError());
+  D2H back(ctx);
+  HIP_TRY(back.add(out_columns, ocols.p, n * 8));
+  HIP_TRY(back.add(out_values, ovals.p, n * 8));
+  HIP_TRY(back.finish());
+  return FBK_OK;
+} FBK_ABI_CATCH(ctx)
+
+int32_t fbk_extract_open_columns(fbk_ctx* ctx, const uint64_t* columns, uint64_t n, const uint64_t* shard_ids, uint32_t n_shards, fbk_extract** out,
+                                 uint32_t* out_rank) try {
+  FBK_ENTER(ctx);
+  if (!out || (n && (!columns || !out_rank)) || (n_shards && !shard_ids)) return fail(FBK_E_INVALID, "NULL argument");
+  *out = nullptr;
+  if (n >= (1ull << 31)) return fail(FBK_E_INVALID, "extract: " + std::to_string(n) + " columns; one handle takes fewer than 2^31");
+  for (uint32_t s = 0; s < n_shards; ++s) {
+    if (shard_ids[s] >= (1ull << 44)) return fail(FBK_E_INVALID, "extract: shard id >= 2^44 (column ids are shard * 2^20 + position)");
+    if (s && shard_ids[s] <= shard_ids[s - 1]) return fail(FBK_E_INVALID, "extract: shard_ids must be strictly ascending");
+  }
+  if (!ctx) return fail(FBK_E_INVALID, "NULL argument");
+  // the slot of every column in ascending order; duplicates and foreign shards are errors
+  std::vector<uint32_t> order(n);
+  for (uint64_t k = 0; k < n; ++k) order[k] = uint32_t(k);
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return columns[a] < columns[b]; });
+  for (uint64_t k = 1; k < n; ++k)
+    if (columns[order[k]] == columns[order[k - 1]]) return fail(FBK_E_INVALID, "extract: column " + std::to_string(columns[order[k]]) + " is listed twice");
+  std::vector<uint64_t> bitpos(n);
+  uint32_t s_first = 0;
+  {
+    const uint64_t* cur = shard_ids;
+    for (uint64_t k = 0; k < n; ++k) {
+      const uint64_t c = columns[order[k]], sh = c >> 20;
+      cur = std::lower_bound(cur, shard_ids + n_shards, sh);
+      if (cur == shard_ids + n_shards || *cur != sh) return fail(FBK_E_INVALID, "extract: column " + std::to_string(c) + " lies in a shard that is not in shard_ids");
+      if (k == 0) s_first = uint32_t(cur - shard_ids);
+      bitpos[k] = (uint64_t(cur - shard_ids) - s_first) << 20 | (c & 0xFFFFF);
+      out_rank[order[k]] = uint32_t(k);
+    }
+  }
+  std::unique_ptr<fbk_extract> h(new fbk_extract);
+  h->ctx = ctx, h->n_shards = n_shards;
+  if (n == 0) {
+    *out = h.release();
+    return FBK_OK;
+  }
+  const uint32_t span = uint32_t(bitpos[n - 1] >> 20) + 1;
+  h->n = n, h->s_first = s_first, h->span = span;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+  const uint64_t su_end = uint64_t(span) * fbk::kExtractUnits, n_words = su_end * fbk::kExtractWords;
+  std::vector<uint32_t> iota(span);
+  for (uint32_t i = 0; i < span; ++i) iota[i] = i;
+  DevBuf rows, dpos, unit_pre, shard_tot, shard_base, carry;
+  HIP_TRY(h->ids.alloc(ctx, uint64_t(n_shards) * 8));
+  HIP_TRY(hipMemcpyAsync(h->ids.p, shard_ids, uint64_t(n_shards) * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (int32_t rc = upload_rows(ctx, iota.data(), span, UINT32_MAX, rows)) return rc;
+  HIP_TRY(dpos.alloc(ctx, n * 8));
+  HIP_TRY(hipMemcpyAsync(dpos.p, bitpos.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(h->sel.alloc(ctx, n_words * 8));
+  HIP_TRY(h->upre.alloc(ctx, (su_end + 1) * 4));
+  HIP_TRY(unit_pre.alloc(ctx, su_end * 4));
+  HIP_TRY(shard_tot.alloc(ctx, uint64_t(span) * 4));
+  HIP_TRY(shard_base.alloc(ctx, (uint64_t(span) + 1) * 8));
+  HIP_TRY(carry.alloc(ctx, 8));
+  HIP_TRY(hipMemsetAsync(carry.p, 0, 8, ctx->stream));
+  HIP_TRY(hipMemsetAsync(h->sel.p, 0, n_words * 8, ctx->stream));
+  hipLaunchKernelGGL(fbk::k_extract_scatter, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, dpos.as<u64>(), u64(n), u64(n_words), h->sel.as<u64>());
+  hipLaunchKernelGGL(fbk::k_extract_scan, dim3(span), dim3(1024), 0, ctx->stream, h->sel.as<uint8_t>(), rows.as<uint32_t>(), unit_pre.as<uint32_t>(),
+                     shard_tot.as<uint32_t>());
+  hipLaunchKernelGGL(fbk::k_bsi_cell_scan, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const Slot*>(nullptr), static_cast<const uint32_t*>(nullptr),
+                     shard_tot.as<uint32_t>(), span, shard_base.as<u64>(), carry.as<u64>());
+  hipLaunchKernelGGL(fbk::k_extract_upre, dim3(uint32_t((su_end + 1 + 255) / 256)), dim3(256), 0, ctx->stream, unit_pre.as<uint32_t>(), shard_base.as<u64>(),
+                     u64(su_end), u64(n), h->upre.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(ctx->stream));  // (the host lists above are the sources of the copies)
+  *out = h.release();
+  return FBK_OK;
+} FBK_ABI_CATCH(ctx)
+
+}  // extern "C"

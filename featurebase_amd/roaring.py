@@ -688,6 +688,40 @@ class Context:
                                           C.byref(h), C.byref(n)))
         return Extract(self, h.value, int(n.value), int(rf.size), filt)
 
+    def extract_columns(self, columns, shard_ids) -> Tuple[Extract, np.ndarray]:
+        """Extract over an explicit column list (any order; fbk_extract_open_columns): (handle, rank) where rank[k] is the slot of
+        columns[k] in the handle's ascending order, so `values[rank]` reads a per-field result in the order of the list."""
+        cols = np.ascontiguousarray(columns, dtype=np.uint64)
+        ids = np.ascontiguousarray(shard_ids, dtype=np.uint64)
+        h, rank = C.c_void_p(), np.zeros(cols.size, dtype=np.uint32)
+        L.check(self.lib.fbk_extract_open_columns(self.h, cols.ctypes.data, cols.size, ids.ctypes.data, ids.size, C.byref(h), rank.ctypes.data))
+        return Extract(self, h.value, int(cols.size), int(ids.size), None), rank
+
+    # -- Sort ----------------------------------------------------------------------------------
+    def bsi_sort(self, batch: Batch, base_rows, bit_depth: int, shard_ids, filt: Optional[Batch] = None, rows_f=None, desc: bool = False,
+                 keep_zero: bool = False, offset: int = 0, limit: Optional[int] = None, cap: Optional[int] = None):
+        """Sort(filter, field=, sort-desc=, limit=, offset=) by an int field (fbk_bsi_sort): (columns uint64[n], values int64[n] —
+        Base not added —, total = the columns that take part before offset / limit).  Equal values come in ascending column id.
+        One retry with the reported size when `cap` records were too few."""
+        base = np.ascontiguousarray(base_rows, dtype=np.uint32)
+        ids = np.ascontiguousarray(shard_ids, dtype=np.uint64)
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        assert base.size == ids.size and (rf is None or rf.size == ids.size)
+        flags = (L.SORT_DESC if desc else 0) | (L.SORT_KEEP_ZERO if keep_zero else 0)
+        if cap is None:
+            cap = 1 << 16 if limit is None else min(limit, 1 << 24)
+        n, total = C.c_uint64(), C.c_uint64()
+        for _ in range(2):
+            cols, vals = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.int64)
+            rc = self.lib.fbk_bsi_sort(self.h, batch.h, base.ctypes.data, bit_depth, filt.h if filt is not None else None,
+                                       rf.ctypes.data if rf is not None else None, ids.ctypes.data, ids.size, flags, offset,
+                                       (1 << 64) - 1 if limit is None else limit, cols.ctypes.data, vals.ctypes.data, cap, C.byref(n), C.byref(total))
+            if rc != L.FBK_E_CAPACITY:
+                break
+            cap = int(n.value)
+        L.check(rc)
+        return cols[: n.value].copy(), vals[: n.value].copy(), int(total.value)
+
     # -- GroupBy with aggregate=Sum ------------------------------------------------------------
     def _msum_args(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, filt: Optional[Batch], rows_f):
         ra = np.ascontiguousarray(rows_a, dtype=np.uint32)

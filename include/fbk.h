@@ -58,7 +58,8 @@ extern "C" {
  *   6 (round 6): + fbk_comm_unique_id / fbk_comm_init / fbk_comm_all_reduce_u64 / fbk_comm_fence / fbk_comm_close (the
  *      one-process-per-GPU exchange issued by the library itself).  fbk_batch_compact refuses a batch of another context;
  *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
- *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free.
+ *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free; fbk_bsi_sort;
+ *      fbk_extract_open_columns.
  *   5 (round 5): + fbk_topn_partials, options topn_semantics, matrix_shadow_arena_x.  CHANGED: fbk_topn / fbk_query_topn /
  *      fbk_group_topn with 0 < n < n_a return the reference's two-pass answer by default (topn_semantics = 1; = 0 restores
  *      round 4's exact top n of fbk_topn; round 4's per-member candidate rule of fbk_group_topn is gone — it was neither);
@@ -618,6 +619,53 @@ int32_t fbk_extract_bsi(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* bsi, cons
 int32_t fbk_extract_rows(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, uint64_t* out_offsets,
                          uint32_t* out_items, uint64_t cap, uint64_t* out_n_items);
 int32_t fbk_extract_free(fbk_ctx* ctx, fbk_extract* h);
+
+/* fbk_extract_open_columns: a handle that selects exactly columns[0 .. n) (any order, n < 2^31) instead of a filter's bits: the
+ * winners of fbk_bsi_sort for Extract(Sort(...), Rows(f), ...) (executor.go:4686-4700, :4762-4769), or the list of
+ * Extract(ConstRow(columns=[...]), ...) (:5604-5694).  shard_ids as fbk_extract_open; a column whose shard (column >> 20) is not in
+ * shard_ids, or one listed twice, is FBK_E_INVALID.  out_rank[k] (n entries) = the slot of columns[k] in the handle's ASCENDING
+ * column order: the per-field calls answer in that order, so record k of the caller's list is slot out_rank[k] of their outputs.
+ * Span (the shards between the smallest and the largest listed column), residency and every per-field call are those of a handle
+ * from fbk_extract_open; base_rows / rows_a of the per-field calls are [n_shards] / [n_shards][n_a] over the shard_ids given here.
+ * The bits are ORed into the handle's words on the device (distinct bits: the result does not depend on the order). */
+int32_t fbk_extract_open_columns(fbk_ctx* ctx, const uint64_t* columns, uint64_t n, const uint64_t* shard_ids, uint32_t n_shards,
+                                 fbk_extract** out, uint32_t* out_rank);
+
+/* ---- Sort(filter, field=, sort-desc=, limit=, offset=) by an int field ---------------------------
+ * executeSort / executeSortShard / SortedRow.Merge (executor.go:9321-9385, :9387-9538, :9574-9608, fragment.go:2878-2969): the
+ * columns of exists ∩ filter ordered by the field's value, then offset, then limit.  The reference sorts every shard and merges
+ * whole shard results before it cuts; this call SELECTS: K = min(offset + limit, total) candidates are found by a radix select
+ * over the bit planes (ceil((bit_depth + 1) / 11) passes, 64-bit keys for bit_depth 63 and 64), only they are sorted, and only
+ * the records of ranks [offset, K) leave the device.
+ *  - Field layout as fbk_bsi_sum (base_rows[s] + 0 exists, + 1 sign, + 2 + i plane i; bit_depth 0..64); shard_ids as
+ *    fbk_extract_open (strictly ascending, < 2^44, column = shard id * 2^20 + position; at most 2^20 shards per call).
+ *    filter == NULL: every column of exists.  Dense and encoded batches both work; what is not dense is densified a chunk of
+ *    shards at a time by fbk_extract_*'s rule with R = (field encoded ? bit_depth + 2 : 0) + (filter encoded ? 1 : 0).
+ *  - out_values[k] is exactly fbk_extract_bsi's value of out_columns[k]: sign ? -magnitude : magnitude, int64 wrap-around (bit_depth
+ *    64: magnitudes >= 2^63 order as the negative numbers they wrap to), Base NOT added.  Sign and plane bits outside exists are
+ *    ignored.
+ *  - KEPT REFERENCE QUIRK (default): a column whose magnitude is 0 does NOT take part, with or without its sign bit:
+ *    flattenRowValues (fragment.go:2943-2969) builds its column -> value map from the set PLANE bits only, so a stored 0 never
+ *    reaches RowKVs.  FBK_SORT_KEEP_ZERO keeps those columns with value 0: what ORDER BY of a SQL caller means.
+ *  - Order: value ascending, FBK_SORT_DESC descending.  Columns of EQUAL value come in ascending column id, in both directions and
+ *    across shards.  The reference leaves this unspecified (Go map iteration order under a stable sort, and SortedRow.Merge takes
+ *    the OTHER shard's record first on a tie): fixed here, as TopN's ties were.
+ *  - offset, then limit, on that global order (executor.go:9367-9383).  limit == UINT64_MAX: no limit.  offset past the end or
+ *    limit == 0: *out_n = 0 (the reference panics or slices past len there; not copied).
+ *  - *out_n = the records of the result, always set; cap < *out_n -> FBK_E_CAPACITY, out_columns / out_values untouched (the
+ *    fbk_bsi_distinct convention).  *out_total (may be NULL) = the columns that take part, before offset / limit.
+ *  - K must be below 2^31, else FBK_E_INVALID (the message says to use a limit).  The TOTAL is not capped.  Device scratch, with
+ *    n_less <= K the columns below the K-th value and n = *out_n:
+ *      2^14 + 2^23 (histograms) + 2^15 * n_shards + chunk (<= 2^28, 0 if both batches are dense) + 16 K + 16 n_less + radix sort temporary (~16 n_less)
+ *      + 16 n + 4 * (row lists) bytes: no key or value per filtered column.
+ *  - The result does not depend on grid size, chunking or the order in which blocks run: histogram counts are sums of per-block
+ *    counts (integer addition commutes), every candidate's slot is its rank from popcount prefixes, the device sort is stable.
+ *  - Bool, mutex and keyed fields are not sorted here (the reference's bool comparison, fragment.go:2890-2894, is not an order). */
+#define FBK_SORT_DESC 1u
+#define FBK_SORT_KEEP_ZERO 2u
+int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, const fbk_batch* filter,
+                     const uint32_t* rows_f, const uint64_t* shard_ids, uint32_t n_shards, uint32_t flags, uint64_t offset,
+                     uint64_t limit, uint64_t* out_columns, int64_t* out_values, uint64_t cap, uint64_t* out_n, uint64_t* out_total);
 
 /* ---- BSI (bit-sliced integers) ----------------------------------------------------------------
  * A BSI fragment of shard s occupies bit_depth+2 consecutive rows of `batch` starting at

@@ -11,6 +11,7 @@
 //   executeTopN (counts; the rank cache is not mirrored)   executor.go:2776-2868
 //   executeGroupBy (groupByIterator odometer)    executor.go:3918-3990, 8617-8934
 //   executeExtract (+ executeLimitCall)          executor.go:4711-5046, 1027-1100
+//   executeSort (+ Extract(Sort(...), ...))      executor.go:9321-9385, 4686-4700, 4762-4769
 // Every shard of a query is evaluated in ONE device call per operator (the reference maps a
 // closure over shards, executor.go:6449); the cross-shard reduce is the same associative
 // arithmetic (sum of counts, ValCount.Add/Smaller/Larger, concatenation of row segments).
@@ -66,6 +67,12 @@ struct ExtractedIDColumn {
 struct ExtractedIDMatrix {
   std::vector<std::string> Fields;
   std::vector<ExtractedIDColumn> Columns;
+};
+
+// Sort's result (executor.go SortedRow.RowKVs): the columns in sort order and their values (Base added)
+struct SortedRow {
+  std::vector<uint64_t> Columns;
+  std::vector<int64_t> Values;
 };
 
 // A PQL bitmap call (the subset on the hot path).
@@ -568,15 +575,83 @@ class Executor {
     const size_t n = shards().size();
     if (n == 0) return out;
     RowSet fr = eval(filter);
-    struct Handle {
-      fbk_ctx* ctx;
-      fbk_extract* h = nullptr;
-      ~Handle() { fbk_extract_free(ctx, h); }
-    } hd{idx_.ctx_};
+    ExtractHandle hd{idx_.ctx_};
     uint64_t cnt = 0;
     check(fbk_extract_open(idx_.ctx_, fr.batch(), fr.rows().data(), shards().data(), uint32_t(n), offset, limit, &hd.h, &cnt));
     std::vector<uint64_t> cols(cnt);
     check(fbk_extract_columns(idx_.ctx_, hd.h, cols.data()));
+    fill_fields(hd.h, cols, nullptr, fields, out);
+    return out;
+  }
+
+  // ---- Sort -----------------------------------------------------------------------------------
+  // Sort(filter, field=, sort-desc=, limit=, offset=) (executeSort, executor.go:9321-9385): the columns of exists ∩ filter in the
+  // order of the field's value, offset then limit; Values carry Base.  Int, decimal and timestamp fields are all BSI fields and
+  // share this path (the mirror stores their integer form).  One fbk_bsi_sort over every shard: the device selects the
+  // offset + limit smallest, only the records of the result come back.  Columns of equal value come in ascending id (the
+  // reference: unspecified); a stored value equal to Base does not take part unless keep_zero (the reference's behaviour, fbk.h).
+  SortedRow Sort(const std::string& field, const Call* filter = nullptr, bool desc = false, uint64_t limit = UINT64_MAX, uint64_t offset = 0,
+                 bool keep_zero = false) {
+    Scope sc(*this, {filter});
+    const Index::IntField& f = idx_.ints_.at(field);
+    SortedRow out;
+    const size_t n = shards().size();
+    if (n == 0) return out;
+    const std::vector<uint32_t> base = base_rows(f);
+    std::optional<RowSet> fr;
+    if (filter) fr.emplace(eval(*filter));
+    const uint32_t flags = (desc ? FBK_SORT_DESC : 0u) | (keep_zero ? FBK_SORT_KEEP_ZERO : 0u);
+    uint64_t cnt = 0, cap = limit < 4096 ? limit : 4096;
+    for (;;) {
+      out.Columns.assign(cap, 0);
+      out.Values.assign(cap, 0);
+      const int32_t rc = fbk_bsi_sort(idx_.ctx_, f.batch, base.data(), f.bit_depth, fr ? fr->batch() : nullptr, fr ? fr->rows().data() : nullptr,
+                                      shards().data(), uint32_t(n), flags, offset, limit, out.Columns.data(), out.Values.data(), cap, &cnt, nullptr);
+      if (rc == FBK_E_CAPACITY) {
+        cap = cnt;
+        continue;
+      }
+      check(rc);
+      break;
+    }
+    out.Columns.resize(cnt);
+    out.Values.resize(cnt);
+    for (int64_t& v : out.Values) v += f.base;
+    return out;
+  }
+
+  // Extract(Sort(filter, field=, sort-desc=, limit=, offset=), Rows(f0), ...) (executor.go:4686-4700, :4762-4769): the records in
+  // SORT order.  The reference extracts every field for every sorted column of every shard and cuts afterwards; here offset and
+  // limit are applied by the sort BEFORE any field is extracted: one fbk_bsi_sort, one fbk_extract_open_columns on the winners,
+  // then one pass per field over the winners' shards only.
+  ExtractedIDMatrix ExtractSorted(const std::string& sort_field, const Call* filter, bool desc, const std::vector<std::string>& fields,
+                                  uint64_t limit = UINT64_MAX, uint64_t offset = 0, bool keep_zero = false) {
+    for (const std::string& name : fields)
+      if (!idx_.sets_.count(name) && !idx_.ints_.count(name)) throw Error(FBK_E_INVALID, "field not found: " + name);  // ErrFieldNotFound
+    Scope sc(*this, {filter});
+    ExtractedIDMatrix out;
+    out.Fields = fields;
+    if (shards().empty()) return out;
+    const SortedRow sorted = Sort(sort_field, filter, desc, limit, offset, keep_zero);
+    ExtractHandle hd{idx_.ctx_};
+    std::vector<uint32_t> rank(sorted.Columns.size());
+    check(fbk_extract_open_columns(idx_.ctx_, sorted.Columns.data(), sorted.Columns.size(), shards().data(), uint32_t(shards().size()), &hd.h, rank.data()));
+    fill_fields(hd.h, sorted.Columns, &rank, fields, out);
+    return out;
+  }
+
+ private:
+  struct ExtractHandle {
+    fbk_ctx* ctx;
+    fbk_extract* h = nullptr;
+    ~ExtractHandle() { fbk_extract_free(ctx, h); }
+  };
+  // the per-field calls of a handle: record k of `cols` is slot (rank ? rank[k] : k) of their outputs
+  void fill_fields(fbk_extract* h, const std::vector<uint64_t>& cols, const std::vector<uint32_t>* rank, const std::vector<std::string>& fields,
+                   ExtractedIDMatrix& out) {
+    const size_t n = shards().size();
+    const uint64_t cnt = cols.size();
+    auto slot = [&](uint64_t k) { return rank ? uint64_t((*rank)[k]) : k; };
     out.Columns.resize(cnt);
     for (uint64_t k = 0; k < cnt; ++k) {
       out.Columns[k].ColumnID = cols[k];
@@ -589,9 +664,9 @@ class Executor {
         const std::vector<uint32_t> base = base_rows(f);
         std::vector<int64_t> vals(cnt);
         std::vector<uint8_t> pres(cnt);
-        check(fbk_extract_bsi(idx_.ctx_, hd.h, f.batch, base.data(), f.bit_depth, vals.data(), pres.data()));
+        check(fbk_extract_bsi(idx_.ctx_, h, f.batch, base.data(), f.bit_depth, vals.data(), pres.data()));
         for (uint64_t k = 0; k < cnt; ++k)
-          if (pres[k]) out.Columns[k].Rows[fi] = std::vector<uint64_t>{uint64_t(vals[k] + f.base)};
+          if (pres[slot(k)]) out.Columns[k].Rows[fi] = std::vector<uint64_t>{uint64_t(vals[slot(k)] + f.base)};
         continue;
       }
       const Index::SetField& f = idx_.sets_.at(fields[fi]);
@@ -604,20 +679,17 @@ class Executor {
         const size_t bi = std::min(kSumBlock, nr - i0);
         const std::vector<uint32_t> ra = row_block(rows_a, n, nr, i0, bi);
         uint64_t m = 0;
-        int32_t rc = fbk_extract_rows(idx_.ctx_, hd.h, f.batch, ra.data(), uint32_t(bi), offs.data(), items.data(), items.size(), &m);
+        int32_t rc = fbk_extract_rows(idx_.ctx_, h, f.batch, ra.data(), uint32_t(bi), offs.data(), items.data(), items.size(), &m);
         if (rc == FBK_E_CAPACITY) {
           items.resize(m);
-          rc = fbk_extract_rows(idx_.ctx_, hd.h, f.batch, ra.data(), uint32_t(bi), offs.data(), items.data(), items.size(), &m);
+          rc = fbk_extract_rows(idx_.ctx_, h, f.batch, ra.data(), uint32_t(bi), offs.data(), items.data(), items.size(), &m);
         }
         check(rc);
         for (uint64_t k = 0; k < cnt; ++k)
-          for (uint64_t p = offs[k]; p < offs[k + 1]; ++p) out.Columns[k].Rows[fi]->push_back(f.row_ids[i0 + items[p]]);
+          for (uint64_t p = offs[slot(k)]; p < offs[slot(k) + 1]; ++p) out.Columns[k].Rows[fi]->push_back(f.row_ids[i0 + items[p]]);
       }
     }
-    return out;
   }
-
- private:
   struct GroupAgg {
     std::string sum_field;                  // aggregate=Sum(field)
     std::string distinct_field;             // aggregate=Count(Distinct(X, field))
