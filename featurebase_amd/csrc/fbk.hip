@@ -30,7 +30,6 @@
 #include "fbk_matrix_kernels.hip.h"
 #include "fbk_matrix_mfma.hip.h"
 #include "fbk_matrix_fused.hip.h"
-#include "fbk_matrix_fused.hip.h"
 #include "fbk_matrix_fusedq.hip.h"
 #include "fbk_matrix_sum.hip.h"
 #include "fbk_matrix_distinct.hip.h"
@@ -641,7 +640,7 @@ struct RowsArg {
   uint64_t n;
   uint32_t limit;  // UINT32_MAX: validated by the caller
 };
-int32_t upload_rows_multi(fbk_ctx* ctx, std::initializer_list<RowsArg> args, DevBuf& out, const uint32_t** d) {
+int32_t upload_rows_multi(fbk_ctx* ctx, const std::vector<RowsArg>& args, DevBuf& out, const uint32_t** d) {
   uint64_t total = 0;
   for (const RowsArg& a : args) {
     for (uint64_t i = 0; a.limit != UINT32_MAX && i < a.n; ++i)
@@ -1934,6 +1933,7 @@ int32_t fbk_setop(fbk_ctx* ctx, int32_t op, const fbk_batch* a, const uint32_t* 
 
 }  // extern "C"
 
+#include "fbk_dense_operands.inc"
 #include "fbk_query_api.inc"
 #include "fbk_matrix_sum_api.inc"
 #include "fbk_matrix_distinct_api.inc"

@@ -7,42 +7,15 @@
 //   sel   [span][16384] u64   the filter's words with the selected columns only         2^17 bytes per shard of the span
 //   upre  [span * 1024 + 1]   u32 rank (relative to lo) of every unit's first column    2^12 bytes per shard of the span
 //   ids   [n_shards] u64      the shard ids
-// The per-field calls walk the span only.  Rows of batches that are not dense are densified a chunk at a time (fbk.h documents the
-// arithmetic: the tests rely on it):
-//   per_shard = 2^17 * R, R = the rows densified per shard (filter 1, BSI bit_depth + 2, set field n_a);
-//   per_shard <= kExtractScratch: most = max(1, min(shards, kExtractScratch / per_shard)), chunk = ceil(shards / ceil(shards / most))
-//     shards per launch, all their rows;  else one shard per launch and blocks of kExtractScratch / 2^17 (2048) rows of it.
+// The per-field calls walk the span only.  Rows of batches that are not dense are densified a chunk of shards at a time
+// (fbk_dense_operands.inc) under kExtractScratch; a set field with more rows per shard than that holds (fbk_extract_rows, n_a >
+// 2048) goes one shard per launch and a block of 2048 rows of it.  (fbk.h documents the arithmetic: the tests rely on it.)
 
 namespace {
 
 constexpr uint64_t kExtractScratch = 1ull << 28;
-constexpr uint64_t kExtractRowBytes = uint64_t(fbk::kSlots) * 8192;
-
-struct ExtractChunks {
-  uint32_t shards = 0;  // shards per launch
-  uint32_t rows = 0;    // rows of a shard per launch
-};
-
-ExtractChunks extract_chunks(uint32_t shards, uint32_t rows_per_shard) {
-  ExtractChunks c;
-  const uint64_t per_shard = kExtractRowBytes * rows_per_shard;
-  if (per_shard <= kExtractScratch) {
-    const uint64_t most = std::max<uint64_t>(1, std::min<uint64_t>(shards, per_shard ? kExtractScratch / per_shard : shards));
-    const uint64_t passes = (shards + most - 1) / most;
-    c.shards = uint32_t((shards + passes - 1) / passes), c.rows = rows_per_shard;
-  } else {
-    c.shards = 1, c.rows = uint32_t(kExtractScratch / kExtractRowBytes);
-  }
-  return c;
-}
 
 uint32_t extract_grid(uint64_t units) { return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((units + 3) / 4, 8192))); }
-
-void extract_densify(fbk_ctx* ctx, const fbk_batch* b, const uint32_t* d_rows, uint64_t n_rows, uint8_t* out) {
-  fbk::DensifyArgs dargs{};
-  dargs.src[0] = {b->d_slots, b->d_arena, d_rows, n_rows, out};
-  hipLaunchKernelGGL(fbk::k_densify_rows, dim3(uint32_t((n_rows * fbk::kSlots + 3) / 4)), dim3(256), 0, ctx->stream, dargs);
-}
 
 }  // namespace
 
@@ -72,10 +45,7 @@ int32_t fbk_extract_open(fbk_ctx* ctx, const fbk_batch* filter, const uint32_t* 
   FBK_ENTER(ctx);
   if (!out || !out_n || (n_shards && (!rows_f || !shard_ids))) return fail(FBK_E_INVALID, "NULL argument");
   *out = nullptr, *out_n = 0;
-  for (uint32_t s = 0; s < n_shards; ++s) {
-    if (shard_ids[s] >= (1ull << 44)) return fail(FBK_E_INVALID, "extract: shard id >= 2^44 (column ids are shard * 2^20 + position)");
-    if (s && shard_ids[s] <= shard_ids[s - 1]) return fail(FBK_E_INVALID, "extract: shard_ids must be strictly ascending");
-  }
+  if (int32_t rc = shard_ids_ok(shard_ids, n_shards, "extract")) return rc;
   if (!ctx || !filter) return fail(FBK_E_INVALID, "NULL argument");
   if (int32_t rc = check_rows(rows_f, n_shards, filter->n_rows, "extract filter")) return rc;
   std::unique_ptr<fbk_extract> h(new fbk_extract);
@@ -86,13 +56,11 @@ int32_t fbk_extract_open(fbk_ctx* ctx, const fbk_batch* filter, const uint32_t* 
   }
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  const bool df = !filter->dense;
-  const ExtractChunks ck = extract_chunks(n_shards, 1);
-  std::vector<uint32_t> iota(df ? ck.shards : 0);
-  for (uint32_t i = 0; i < iota.size(); ++i) iota[i] = i;
-  DevBuf rows, unit_pre, shard_tot, shard_base, carry, dense;
-  const uint32_t* d[2];
-  if (int32_t rc = upload_rows_multi(ctx, {{rows_f, n_shards, UINT32_MAX}, {iota.data(), iota.size(), UINT32_MAX}}, rows, d)) return rc;
+  DenseOperands ops;
+  const int kF = ops.add(filter, rows_f, 1);
+  const uint32_t chunk = even_chunk(n_shards, kExtractScratch, kDenseRowBytes * ops.densified_rows());
+  DevBuf unit_pre, shard_tot, shard_base, carry;
+  if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
   HIP_TRY(h->ids.alloc(ctx, uint64_t(n_shards) * 8));
   {
     const void* src = shard_ids;
@@ -107,17 +75,15 @@ int32_t fbk_extract_open(fbk_ctx* ctx, const fbk_batch* filter, const uint32_t* 
   HIP_TRY(shard_base.alloc(ctx, (uint64_t(n_shards) + 1) * 8));
   HIP_TRY(carry.alloc(ctx, 8));
   HIP_TRY(hipMemsetAsync(carry.p, 0, 8, ctx->stream));
-  if (df) HIP_TRY(dense.alloc(ctx, uint64_t(ck.shards) * kExtractRowBytes));
   // the filter's columns per unit and per shard, from its words
-  for (uint32_t s0 = 0; s0 < n_shards; s0 += ck.shards) {
-    const uint32_t ns = df ? std::min(ck.shards, n_shards - s0) : n_shards;
-    if (df) extract_densify(ctx, filter, d[0] + s0, ns, dense.as<uint8_t>());
-    hipLaunchKernelGGL(fbk::k_extract_scan, dim3(ns), dim3(1024), 0, ctx->stream, df ? dense.as<uint8_t>() : filter->d_arena, df ? d[1] : d[0],
-                       unit_pre.as<uint32_t>() + uint64_t(s0) * fbk::kExtractUnits, shard_tot.as<uint32_t>() + s0);
-    if (!df) break;
+  for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
+    const uint32_t ns = std::min(chunk, n_shards - s0);
+    ops.densify(ctx, s0, ns);
+    const DenseView F = ops.view(kF, s0);
+    hipLaunchKernelGGL(fbk::k_extract_scan, dim3(ns), dim3(1024), 0, ctx->stream, F.arena, F.rows, unit_pre.as<uint32_t>() + uint64_t(s0) * fbk::kExtractUnits,
+                       shard_tot.as<uint32_t>() + s0);
   }
-  hipLaunchKernelGGL(fbk::k_bsi_cell_scan, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const Slot*>(nullptr), static_cast<const uint32_t*>(nullptr),
-                     shard_tot.as<uint32_t>(), n_shards, shard_base.as<u64>(), carry.as<u64>());
+  exclusive_scan_u32(ctx, shard_tot.as<uint32_t>(), n_shards, shard_base.as<u64>(), carry.as<u64>());
   HIP_TRY(hipGetLastError());
   std::vector<uint64_t> base(uint64_t(n_shards) + 1);
   {
@@ -141,13 +107,12 @@ int32_t fbk_extract_open(fbk_ctx* ctx, const fbk_batch* filter, const uint32_t* 
   const uint64_t su_end = uint64_t(span) * fbk::kExtractUnits;
   HIP_TRY(h->sel.alloc(ctx, su_end * fbk::kExtractWords * 8));
   HIP_TRY(h->upre.alloc(ctx, (su_end + 1) * 4));
-  for (uint32_t s0 = 0; s0 < span; s0 += ck.shards) {  // (the chunk of the first pass: its buffer and index list)
-    const uint32_t ns = df ? std::min(ck.shards, span - s0) : span;
-    if (df) extract_densify(ctx, filter, d[0] + s_first + s0, ns, dense.as<uint8_t>());
-    hipLaunchKernelGGL(fbk::k_extract_select, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)), dim3(256), 0, ctx->stream,
-                       df ? dense.as<uint8_t>() : filter->d_arena, df ? d[1] : d[0] + s_first + s0, ns, unit_pre.as<uint32_t>(), shard_base.as<u64>(),
-                       s_first + s0, s0, u64(lo), u64(hi), u64(su_end), h->sel.as<u64>(), h->upre.as<uint32_t>());
-    if (!df) break;
+  for (uint32_t s0 = 0; s0 < span; s0 += chunk) {  // (the chunk of the first pass: its scratch and lists)
+    const uint32_t ns = std::min(chunk, span - s0);
+    ops.densify(ctx, s_first + s0, ns);
+    const DenseView F = ops.view(kF, s_first + s0);
+    hipLaunchKernelGGL(fbk::k_extract_select, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)), dim3(256), 0, ctx->stream, F.arena, F.rows, ns,
+                       unit_pre.as<uint32_t>(), shard_base.as<u64>(), s_first + s0, s0, u64(lo), u64(hi), u64(su_end), h->sel.as<u64>(), h->upre.as<uint32_t>());
   }
   HIP_TRY(hipGetLastError());
   *out = h.release();
@@ -187,35 +152,25 @@ int32_t fbk_extract_bsi(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* bsi, cons
   if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
   if (int32_t rc = extract_handle_ok(ctx, h)) return rc;
   if (!bsi || (h->n_shards && !base_rows)) return fail(FBK_E_INVALID, "NULL argument");
-  const uint64_t rps = uint64_t(bit_depth) + 2;
-  for (uint32_t s = 0; s < h->n_shards; ++s)
-    if (uint64_t(base_rows[s]) + rps > bsi->n_rows) return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, h->n_shards, bit_depth, bsi->n_rows)) return rc;
   if (h->n == 0) return FBK_OK;
   if (!out_values || !out_present) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  const bool dd = !bsi->dense;
   const uint32_t span = h->span;
-  const uint32_t* base = base_rows + h->s_first;
-  const ExtractChunks ck = extract_chunks(span, uint32_t(rps));
-  std::vector<uint32_t> all(dd ? uint64_t(span) * rps : 0), ibase(dd ? ck.shards : 0);
-  for (uint32_t s = 0; s < span && dd; ++s)
-    for (uint64_t r = 0; r < rps; ++r) all[uint64_t(s) * rps + r] = uint32_t(base[s] + r);
-  for (uint64_t i = 0; i < ibase.size(); ++i) ibase[i] = uint32_t(i * rps);
-  DevBuf rows, dense, vals, pres;
-  const uint32_t* d[3];
-  if (int32_t rc = upload_rows_multi(ctx, {{base, span, UINT32_MAX}, {all.data(), all.size(), UINT32_MAX}, {ibase.data(), ibase.size(), UINT32_MAX}}, rows, d))
-    return rc;
-  if (dd) HIP_TRY(dense.alloc(ctx, uint64_t(ck.shards) * rps * kExtractRowBytes));
+  DenseOperands ops;
+  const int kS = ops.add(bsi, base_rows + h->s_first, bit_depth + 2, true);
+  const uint32_t chunk = even_chunk(span, kExtractScratch, kDenseRowBytes * ops.densified_rows());
+  DevBuf vals, pres;
+  if (int32_t rc = ops.upload(ctx, span, chunk)) return rc;
   HIP_TRY(vals.alloc(ctx, h->n * 8));
   HIP_TRY(pres.alloc(ctx, h->n));
-  for (uint32_t s0 = 0; s0 < span; s0 += ck.shards) {
-    const uint32_t ns = dd ? std::min(ck.shards, span - s0) : span;
-    if (dd) extract_densify(ctx, bsi, d[1] + uint64_t(s0) * rps, uint64_t(ns) * rps, dense.as<uint8_t>());
-    hipLaunchKernelGGL(fbk::k_extract_bsi, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)), dim3(256), 0, ctx->stream,
-                       dd ? dense.as<uint8_t>() : bsi->d_arena, dd ? d[2] : d[0], ns, s0, bit_depth, h->sel.as<u64>(), h->upre.as<uint32_t>(), u64(h->n),
-                       vals.as<long long>(), pres.as<uint8_t>());
-    if (!dd) break;
+  for (uint32_t s0 = 0; s0 < span; s0 += chunk) {
+    const uint32_t ns = std::min(chunk, span - s0);
+    ops.densify(ctx, s0, ns);
+    const DenseView S = ops.view(kS, s0);
+    hipLaunchKernelGGL(fbk::k_extract_bsi, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, s0, bit_depth,
+                       h->sel.as<u64>(), h->upre.as<uint32_t>(), u64(h->n), vals.as<long long>(), pres.as<uint8_t>());
   }
   HIP_TRY(hipGetLastError());
   D2H back(ctx);
@@ -240,16 +195,15 @@ int32_t fbk_extract_rows(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* a, const
   }
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  const bool da = !a->dense;
   const uint32_t span = h->span;
-  const uint32_t* ra = rows_a + uint64_t(h->s_first) * n_a;
-  const ExtractChunks ck = extract_chunks(span, n_a);
-  std::vector<uint32_t> iota(da ? uint64_t(ck.shards) * ck.rows : 0);
-  for (uint64_t i = 0; i < iota.size(); ++i) iota[i] = uint32_t(i);
-  DevBuf rows, dense, counts, tsum, tbase, carry, offs, items;
-  const uint32_t* d[2];
-  if (int32_t rc = upload_rows_multi(ctx, {{ra, uint64_t(span) * n_a, UINT32_MAX}, {iota.data(), iota.size(), UINT32_MAX}}, rows, d)) return rc;
-  if (da) HIP_TRY(dense.alloc(ctx, uint64_t(ck.shards) * ck.rows * kExtractRowBytes));
+  DenseOperands ops;
+  const int kA = ops.add(a, rows_a + uint64_t(h->s_first) * n_a, n_a);
+  // a chunk of shards and all their rows per launch, or (one shard's rows exceed the scratch) one shard and a block of its rows
+  const uint64_t per_shard = kDenseRowBytes * ops.densified_rows();
+  const bool blocks = per_shard > kExtractScratch;
+  const uint32_t chunk = blocks ? 1 : even_chunk(span, kExtractScratch, per_shard), block = blocks ? uint32_t(kExtractScratch / kDenseRowBytes) : n_a;
+  DevBuf counts, tsum, tbase, carry, offs, items;
+  if (int32_t rc = ops.upload(ctx, span, chunk, block)) return rc;
   const uint64_t n_tiles = (n + 1 + fbk::kExtractTile - 1) / fbk::kExtractTile, padded = n_tiles * fbk::kExtractTile;  // n + 1: offs[n] is the total
   HIP_TRY(counts.alloc(ctx, padded * 4));
   HIP_TRY(tsum.alloc(ctx, n_tiles * 4));
@@ -258,32 +212,27 @@ int32_t fbk_extract_rows(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* a, const
   HIP_TRY(offs.alloc(ctx, (n + 1) * 8));
   // one walk over the span, a chunk of shards and a block of rows per launch: counts (fill == false), then the items
   auto walk = [&](bool fill, u64 m) {
-    for (uint32_t s0 = 0; s0 < span; s0 += ck.shards) {
-      const uint32_t ns = da ? std::min(ck.shards, span - s0) : span;
-      for (uint32_t i0 = 0; i0 < n_a; i0 += ck.rows) {
-        const uint32_t nr = da ? std::min(ck.rows, n_a - i0) : n_a;
-        // (row blocks only with one shard per launch: its rows [i0, i0 + nr) are consecutive in the list)
-        if (da) extract_densify(ctx, a, d[0] + uint64_t(s0) * n_a + i0, uint64_t(ns) * nr, dense.as<uint8_t>());
-        const uint8_t* arena = da ? dense.as<uint8_t>() : a->d_arena;
-        const uint32_t* rr = da ? d[1] : d[0];
+    for (uint32_t s0 = 0; s0 < span; s0 += chunk) {
+      const uint32_t ns = std::min(chunk, span - s0);
+      for (uint32_t i0 = 0; i0 < n_a; i0 += block) {
+        const uint32_t nr = std::min(block, n_a - i0);
+        ops.densify_one(ctx, kA, s0, ns, i0, nr);
+        const DenseView A = ops.view(kA, s0, i0);
         const dim3 grid(extract_grid(uint64_t(ns) * fbk::kExtractUnits));
         if (fill)
-          hipLaunchKernelGGL(fbk::k_extract_rows<true>, grid, dim3(256), 0, ctx->stream, arena, rr, da ? nr : n_a, nr, i0, ns, s0, h->sel.as<u64>(),
+          hipLaunchKernelGGL(fbk::k_extract_rows<true>, grid, dim3(256), 0, ctx->stream, A.arena, A.rows, A.stride, nr, i0, ns, s0, h->sel.as<u64>(),
                              h->upre.as<uint32_t>(), u64(n), counts.as<uint32_t>(), offs.as<u64>(), items.as<uint32_t>(), m);
         else
-          hipLaunchKernelGGL(fbk::k_extract_rows<false>, grid, dim3(256), 0, ctx->stream, arena, rr, da ? nr : n_a, nr, i0, ns, s0, h->sel.as<u64>(),
+          hipLaunchKernelGGL(fbk::k_extract_rows<false>, grid, dim3(256), 0, ctx->stream, A.arena, A.rows, A.stride, nr, i0, ns, s0, h->sel.as<u64>(),
                              h->upre.as<uint32_t>(), u64(n), counts.as<uint32_t>(), static_cast<const u64*>(nullptr), static_cast<uint32_t*>(nullptr), m);
-        if (!da) break;
       }
-      if (!da) break;
     }
   };
   HIP_TRY(hipMemsetAsync(counts.p, 0, padded * 4, ctx->stream));
   HIP_TRY(hipMemsetAsync(carry.p, 0, 8, ctx->stream));
   walk(false, 0);
   hipLaunchKernelGGL(fbk::k_extract_tile_sums, dim3(uint32_t(n_tiles)), dim3(1024), 0, ctx->stream, counts.as<uint32_t>(), tsum.as<uint32_t>());
-  hipLaunchKernelGGL(fbk::k_bsi_cell_scan, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const Slot*>(nullptr), static_cast<const uint32_t*>(nullptr),
-                     tsum.as<uint32_t>(), uint32_t(n_tiles), tbase.as<u64>(), carry.as<u64>());
+  exclusive_scan_u32(ctx, tsum.as<uint32_t>(), uint32_t(n_tiles), tbase.as<u64>(), carry.as<u64>());
   hipLaunchKernelGGL(fbk::k_extract_offsets, dim3(uint32_t(n_tiles)), dim3(1024), 0, ctx->stream, counts.as<uint32_t>(), tbase.as<u64>(), u64(n + 1),
                      offs.as<u64>());
   HIP_TRY(hipGetLastError());

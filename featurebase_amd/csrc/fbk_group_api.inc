@@ -512,9 +512,7 @@ int32_t fbk_group_bsi_sum(fbk_group* g, const fbk_bsi_args* per_member, uint32_t
     if (!a.batch || !a.base_rows || (a.filter && !a.rows_f)) return fail(FBK_E_INVALID, "group: NULL argument for member " + std::to_string(m));
     if (a.batch->ctx != g->members[m] || (a.filter && a.filter->ctx != g->members[m]))
       return fail(FBK_E_INVALID, "group: the batches of member " + std::to_string(m) + " live on another context");
-    for (uint32_t s = 0; s < a.n_shards; ++s)
-      if (uint64_t(a.base_rows[s]) + 2 + bit_depth > a.batch->n_rows)
-        return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+    if (int32_t rc = bsi_rows_ok(a.base_rows, a.n_shards, bit_depth, a.batch->n_rows)) return rc;
   }
   MemberLocks locks(g);
   int32_t rc = group_reserve(g, 3);

@@ -6,16 +6,15 @@
 //   1. the sorted distinct values U of exists ∩ F over all shards (bsi_distinct_device: fbk_bsi_distinct's kernels, unchanged);
 //   2. per tile of the presence bitmap, k_mdist_scatter over the operands of every shard, then k_mdist_popcount;
 //   3. (out_counts) fbk_count_matrix_sum's count pass: k_msum_mfma without value chunks, exists as the bit planes' row.
-// Operands of batches that are not dense are densified a chunk of shards at a time (k_densify_rows): in stage 1 by
+// Operands of batches that are not dense are densified a chunk of shards at a time (fbk_dense_operands.inc): in stage 1 by
 // bsi_distinct_device (the BSI rows and the filter), in stage 2 again (every operand; stage 2 needs U first), in stage 3 by the
 // count pass.  Stage 2's arithmetic (fbk.h documents it: the tests rely on it):
 //   presence tile: wb = ceil(n_b / 64) words per (A row, rank), m64 = m rounded up to 64, row = 8 * wb * m64 bytes per A row;
 //     n_a * row <= kMdistPresence: one tile;  else 64 * row <= kMdistPresence: ta = floor(kMdistPresence / row) rounded down
 //     to a multiple of 64 A rows, all ranks;  else ta = min(n_a, 64) A rows, tr = floor(kMdistPresence / (8 * wb * ta))
 //     rounded down to a multiple of 64 ranks.
-//   densify chunk: per shard 128 KiB per densified row (n_a, n_b, 1 filter row, depth + 2 BSI rows, each for the batches that
-//     are not dense); most = max(1, min(n_shards, kMdistScratch / that)), chunk = ceil(n_shards / ceil(n_shards / most)).
-//     With more than one chunk, every tile densifies every chunk again.
+//   densify chunk: 128 KiB per densified row of a shard, at most kMdistScratch.  With more than one chunk, every tile densifies
+//     every chunk again.
 
 namespace {
 
@@ -63,38 +62,11 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
   if (int32_t rc = bsi_distinct_device(ctx, bsi, base_rows, n_shards, bit_depth, filter, rows_f, duniq, m)) return rc;
   if (m > 0) {
     // stage 2: operands (densified a chunk of shards at a time), presence tiles
-    const bool da = !a->dense, db = b && !b->dense, df = filter && !filter->dense, dbsi = !bsi->dense;
-    const uint64_t row_bytes = uint64_t(fbk::kSlots) * 8192, rps = uint64_t(bit_depth) + 2;
-    const uint64_t per_shard = row_bytes * ((da ? n_a : 0) + (db ? n_b : 0) + (df ? 1 : 0) + (dbsi ? rps : 0));
-    const uint64_t most = per_shard ? std::max<uint64_t>(1, std::min<uint64_t>(n_shards, kMdistScratch / per_shard)) : n_shards;
-    const uint64_t passes = (n_shards + most - 1) / most;
-    const uint32_t chunk = uint32_t((n_shards + passes - 1) / passes);
-    std::vector<uint32_t> ia(da ? uint64_t(chunk) * n_a : 0), ib(db ? uint64_t(chunk) * n_b : 0), i1(chunk), ibase(dbsi ? chunk : 0),
-        all(dbsi ? uint64_t(n_shards) * rps : 0);
-    for (uint64_t i = 0; i < ia.size(); ++i) ia[i] = uint32_t(i);
-    for (uint64_t i = 0; i < ib.size(); ++i) ib[i] = uint32_t(i);
-    for (uint32_t i = 0; i < chunk; ++i) i1[i] = i;
-    for (uint64_t i = 0; i < ibase.size(); ++i) ibase[i] = uint32_t(i * rps);
-    for (uint32_t s = 0; s < n_shards && dbsi; ++s)
-      for (uint64_t r = 0; r < rps; ++r) all[uint64_t(s) * rps + r] = uint32_t(base_rows[s] + r);
-    DevBuf rows, ta, tb, tf, tbsi, pres, result;
-    const uint32_t* d[9];
-    if (int32_t rc = upload_rows_multi(ctx,
-                                       {{rows_a, uint64_t(n_shards) * n_a, UINT32_MAX},
-                                        {rows_b, b ? uint64_t(n_shards) * n_b : 0, UINT32_MAX},
-                                        {rows_f, filter ? uint64_t(n_shards) : 0, UINT32_MAX},
-                                        {base_rows, n_shards, UINT32_MAX},
-                                        {ia.data(), ia.size(), UINT32_MAX},
-                                        {ib.data(), ib.size(), UINT32_MAX},
-                                        {i1.data(), i1.size(), UINT32_MAX},
-                                        {ibase.data(), ibase.size(), UINT32_MAX},
-                                        {all.data(), all.size(), UINT32_MAX}},
-                                       rows, d))
-      return rc;
-    if (da) HIP_TRY(ta.alloc(ctx, uint64_t(chunk) * n_a * row_bytes));
-    if (db) HIP_TRY(tb.alloc(ctx, uint64_t(chunk) * n_b * row_bytes));
-    if (df) HIP_TRY(tf.alloc(ctx, uint64_t(chunk) * row_bytes));
-    if (dbsi) HIP_TRY(tbsi.alloc(ctx, uint64_t(chunk) * rps * row_bytes));
+    DenseOperands ops;
+    const int kA = ops.add(a, rows_a, n_a), kB = ops.add(b, rows_b, n_b), kF = ops.add(filter, rows_f, 1), kS = ops.add(bsi, base_rows, bit_depth + 2, true);
+    const uint32_t chunk = even_chunk(n_shards, kMdistScratch, kDenseRowBytes * ops.densified_rows());
+    if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
+    DevBuf pres, result;
     const MdistTiles t = mdist_tiles(n_a, n_b, m);
     const uint32_t wb = (n_b + 63) / 64, tr = uint32_t(t.tr);
     const uint64_t m64 = (m + 63) / 64 * 64;
@@ -108,39 +80,12 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
         HIP_TRY(hipMemsetAsync(pres.p, 0, uint64_t(na) * wb * tr * 8, ctx->stream));
         for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
           const uint32_t ns = std::min(chunk, n_shards - s0);
-          const uint8_t *arA = a->d_arena, *arB = b ? b->d_arena : nullptr, *arF = filter ? filter->d_arena : nullptr, *arS = bsi->d_arena;
-          const uint32_t *ra = d[0] + uint64_t(s0) * n_a, *rb = b ? d[1] + uint64_t(s0) * n_b : nullptr, *rf = filter ? d[2] + s0 : nullptr,
-                         *rs = d[3] + s0;
-          std::vector<fbk::DensifySrc> srcs;
-          if (da) {
-            srcs.push_back({a->d_slots, a->d_arena, ra, uint64_t(ns) * n_a, ta.as<uint8_t>()});
-            arA = ta.as<uint8_t>(), ra = d[4];
-          }
-          if (db) {
-            srcs.push_back({b->d_slots, b->d_arena, rb, uint64_t(ns) * n_b, tb.as<uint8_t>()});
-            arB = tb.as<uint8_t>(), rb = d[5];
-          }
-          if (df) {
-            srcs.push_back({filter->d_slots, filter->d_arena, rf, uint64_t(ns), tf.as<uint8_t>()});
-            arF = tf.as<uint8_t>(), rf = d[6];
-          }
-          if (dbsi) {
-            srcs.push_back({bsi->d_slots, bsi->d_arena, d[8] + uint64_t(s0) * rps, uint64_t(ns) * rps, tbsi.as<uint8_t>()});
-            arS = tbsi.as<uint8_t>(), rs = d[7];
-          }
-          for (size_t k0 = 0; k0 < srcs.size() && !densified; k0 += 3) {
-            fbk::DensifyArgs dargs{};
-            uint64_t cells = 0;
-            for (size_t k = k0; k < std::min(srcs.size(), k0 + 3); ++k) {
-              dargs.src[k - k0] = srcs[k];
-              cells += srcs[k].n_rows * fbk::kSlots;
-            }
-            hipLaunchKernelGGL(fbk::k_densify_rows, dim3(uint32_t((cells + 3) / 4)), dim3(256), 0, ctx->stream, dargs);
-          }
-          densified = passes == 1;
+          if (!densified) ops.densify(ctx, s0, ns);
+          densified = chunk == n_shards;
+          const DenseView A = ops.view(kA, s0), B = ops.view(kB, s0), F = ops.view(kF, s0), S = ops.view(kS, s0);
           const uint64_t units = uint64_t(ns) * (fbk::kSlots * 1024 / fbk::kMdistWords);
           const uint32_t grid = uint32_t(std::min<uint64_t>((units + 3) / 4, 2048));
-          hipLaunchKernelGGL(fbk::k_mdist_scatter, dim3(grid), dim3(256), 0, ctx->stream, arA, ra, n_a, a0, na, arB, rb, n_b, arF, rf, arS, rs,
+          hipLaunchKernelGGL(fbk::k_mdist_scatter, dim3(grid), dim3(256), 0, ctx->stream, A.arena, A.rows, n_a, a0, na, B.arena, B.rows, n_b, F.arena, F.rows, S.arena, S.rows,
                              bit_depth, duniq.as<long long>(), uint32_t(m), uint32_t(r0), tr, ns, pres.as<u64>());
         }
         // popcount: enough parts of the rank range for ~8192 wavefronts

@@ -204,8 +204,7 @@ int32_t fbk_query_bsi_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* 
   if (n_shards == 0) return fail(FBK_E_INVALID, "query: no shards");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  for (uint32_t s = 0; s < n_shards; ++s)
-    if (uint64_t(base_rows[s]) + 2 + bit_depth > batch->n_rows) return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
   fbk_query* q = new (std::nothrow) fbk_query();
   if (!q) return fail(FBK_E_NOMEM, "host allocation failed");
   q->ctx = ctx;
@@ -253,8 +252,7 @@ int32_t fbk_query_bsi_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t
   }
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  for (uint32_t s = 0; s < n_shards; ++s)
-    if (uint64_t(base_rows[s]) + 2 + bit_depth > batch->n_rows) return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
   fbk_query* q = new (std::nothrow) fbk_query();
   if (!q) return fail(FBK_E_NOMEM, "host allocation failed");
   q->ctx = ctx;

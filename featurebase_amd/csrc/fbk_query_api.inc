@@ -472,9 +472,7 @@ bool plan_between_sum(uint64_t depth, int64_t lo, int64_t hi, fbk::BetweenSumPla
 int32_t run_bsi_program(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint64_t n_shards,
                         uint64_t bit_depth, const BsiProg& prog, uint32_t flags, fbk_batch** out_batch,
                         uint64_t* out_counts) {
-  for (uint64_t s = 0; s < n_shards; ++s)
-    if (uint64_t(base_rows[s]) + 2 + bit_depth > batch->n_rows)
-      return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
   fbk_batch* o = nullptr;
   if (int32_t rc = alloc_cell_batch(ctx, n_shards, &o)) return rc;
   DevBuf dbase, dprog, druns, dcnt;
@@ -687,7 +685,7 @@ int32_t fbk_union_n_intersection_count(fbk_ctx* ctx, const fbk_batch* batch, con
 // (profiles/r04_small_shapes_ab.json): the fused kernel costs 65-75 us whatever the shape up to a 32 x 32 tile (it decodes
 // every row once), the generic kernel ~38 us + 1.5 us per pair — 2 x 2: 44 against 65 us, 8 x 8: 139 against 70, 4 x 16: 156
 // against 70, 3 x 30: 241 against 73.  From 16 pairs per shard on the rows are decoded once.  (Rounds 1-4 had a third path —
-// k_densify_rows into temporary bitmap rows, then the dense kernel: 681 + 347 us against ~400 us for the first in-kernel
+// rows densified into temporary bitmap rows, then the dense kernel: 681 + 347 us against ~400 us for the first in-kernel
 // decode on 256 shards of config 3's rows, never chosen since round 2 — removed in round 5.)
 static bool matrix_prefers_fused(uint32_t n_a, uint32_t n_b) { return uint64_t(n_a) * n_b >= 16; }
 
@@ -1497,9 +1495,7 @@ int32_t fbk_bsi_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_r
   if (n_shards == 0) return FBK_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  for (uint32_t s = 0; s < n_shards; ++s)
-    if (uint64_t(base_rows[s]) + 2 + bit_depth > batch->n_rows)
-      return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
   DevBuf dbase, drf, d3;
   if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
   if (filter)
@@ -1528,9 +1524,7 @@ static int32_t bsi_minmax(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* 
   if (n_shards == 0) return FBK_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  for (uint32_t s = 0; s < n_shards; ++s)
-    if (uint64_t(base_rows[s]) + 2 + bit_depth > batch->n_rows)
-      return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
   DevBuf dbase, drf, d2;
   if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
   if (filter)
@@ -1705,75 +1699,41 @@ static int32_t bsi_distinct_device(fbk_ctx* ctx, const fbk_batch* batch, const u
   fbk_batch* bb = const_cast<fbk_batch*>(batch);
   if (int32_t rc = refresh_slots(bb)) return rc;
   uint64_t upper = 0;  // at most one value per existing column
-  for (uint32_t s = 0; s < n_shards; ++s) {
-    if (uint64_t(base_rows[s]) + 2 + bit_depth > batch->n_rows)
-      return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
+  for (uint32_t s = 0; s < n_shards; ++s)
     for (int sl = 0; sl < fbk::kSlots; ++sl) upper += fbk::slot_n(batch->h_slots[uint64_t(base_rows[s]) * fbk::kSlots + sl]);
-  }
   if (filter)
     if (int32_t rc = check_rows(rows_f, n_shards, filter->n_rows, "bsi_distinct filter")) return rc;
   if (upper == 0) return FBK_OK;
   if (upper >= (1ull << 31)) return fail(FBK_E_INVALID, "bsi_distinct: more than 2^31 values in one call (split the shard list)");
-  DevBuf dvals, dsorted, dcur, dtmp, drows, dfrows, ta, tf, dbase, dcounts;
+  DevBuf dvals, dsorted, dcur, dtmp, dbase, dcounts;
   HIP_TRY(dvals.alloc(ctx, upper * 8));
   HIP_TRY(dcur.alloc(ctx, 32));  // [0] the running total of values (k_bsi_cell_scan's carry), [1] the number of distinct values, [2] (uint32) the count-mismatch flag
   HIP_TRY(hipMemsetAsync(dcur.p, 0, 32, ctx->stream));
   HIP_TRY(dbase.alloc(ctx, (uint64_t(n_shards) * fbk::kSlots + 1) * 8));
   if (filter) HIP_TRY(dcounts.alloc(ctx, uint64_t(n_shards) * fbk::kSlots * 4));
   uint32_t* d_flag = reinterpret_cast<uint32_t*>(dcur.as<u64>() + 2);
-  const uint64_t row_bytes = uint64_t(fbk::kSlots) * 8192;
+  // Array / run containers among the planes or in the filter: both are densified, a chunk of shards at a time (<= ~4 GiB).
+  const bool densify = !batch->dense || (filter && !filter->dense);
   const uint32_t rps = bit_depth + 2;  // rows per shard
-  const bool fdense = !filter || filter->dense;
+  const uint32_t chunk = densify ? uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(n_shards, (4ull << 30) / ((rps + 1) * kDenseRowBytes)))) : n_shards;
+  DenseOperands ops;
+  const int kS = ops.add(batch, base_rows, rps, true, densify), kF = ops.add(filter, rows_f, 1, false, densify);
+  if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
   // Where a cell's values go is known before the transpose runs (k_bsi_cell_scan): without a filter the stored cardinalities of the
   // exists row are the counts, with one a count pass over exists ∩ filter comes first.
-  if (batch->dense && fdense) {
-    if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, drows)) return rc;
-    if (filter) {
-      if (int32_t rc = upload_rows(ctx, rows_f, n_shards, filter->n_rows, dfrows)) return rc;
-      hipLaunchKernelGGL(fbk::k_bsi_cell_counts, dim3((n_shards * fbk::kSlots + 3) / 4), dim3(256), 0, ctx->stream, batch->d_arena, drows.as<uint32_t>(), n_shards,
-                         filter->d_arena, dfrows.as<uint32_t>(), dcounts.as<uint32_t>());
-    }
-    hipLaunchKernelGGL(fbk::k_bsi_cell_scan, dim3(1), dim3(1024), 0, ctx->stream, batch->d_slots, drows.as<uint32_t>(),
-                       filter ? dcounts.as<uint32_t>() : (const uint32_t*)nullptr, n_shards * fbk::kSlots, dbase.as<u64>(), dcur.as<u64>());
-    hipLaunchKernelGGL(fbk::k_bsi_values, dim3(n_shards * fbk::kSlots * bsi_values_split(n_shards)), dim3(256), 0, ctx->stream, batch->d_arena, drows.as<uint32_t>(),
-                       n_shards, bit_depth, filter ? filter->d_arena : (const uint8_t*)nullptr, dfrows.as<uint32_t>(),
-                       dvals.as<long long>(), u64(upper), dbase.as<u64>(), d_flag, bsi_values_split(n_shards));
-  } else {
-    // array / run containers among the planes: densify a chunk of shards at a time (<= ~4 GiB)
-    const uint32_t chunk = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(n_shards, (4ull << 30) / ((rps + 1) * row_bytes))));
-    HIP_TRY(ta.alloc(ctx, uint64_t(chunk) * rps * row_bytes));
-    if (filter) HIP_TRY(tf.alloc(ctx, uint64_t(chunk) * row_bytes));
-    std::vector<uint32_t> all(uint64_t(n_shards) * rps), ident(chunk), fident(chunk);
-    for (uint32_t s = 0; s < n_shards; ++s)
-      for (uint32_t r = 0; r < rps; ++r) all[uint64_t(s) * rps + r] = base_rows[s] + r;
-    for (uint32_t c = 0; c < chunk; ++c) {
-      ident[c] = c * rps;
-      fident[c] = c;
-    }
-    DevBuf dall, dident, dfident;
-    if (int32_t rc = upload_rows(ctx, all.data(), all.size(), batch->n_rows, dall)) return rc;
-    if (int32_t rc = upload_rows(ctx, ident.data(), chunk, UINT32_MAX, dident)) return rc;
-    if (int32_t rc = upload_rows(ctx, fident.data(), chunk, UINT32_MAX, dfident)) return rc;
-    if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, drows)) return rc;
+  for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
+    const uint32_t ns = std::min(chunk, n_shards - s0);
+    ops.densify(ctx, s0, ns);
+    const DenseView S = ops.view(kS, s0), F = ops.view(kF, s0);
+    u64* cb = dbase.as<u64>() + uint64_t(s0) * fbk::kSlots;  // (the chunk's last entry is the next chunk's first: the same number)
     if (filter)
-      if (int32_t rc = upload_rows(ctx, rows_f, n_shards, filter->n_rows, dfrows)) return rc;
-    for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-      const uint32_t ns = std::min(chunk, n_shards - s0);
-      fbk::DensifyArgs da{};
-      da.src[0] = fbk::DensifySrc{batch->d_slots, batch->d_arena, dall.as<uint32_t>() + uint64_t(s0) * rps, uint64_t(ns) * rps, ta.as<uint8_t>()};
-      if (filter) da.src[1] = fbk::DensifySrc{filter->d_slots, filter->d_arena, dfrows.as<uint32_t>() + s0, uint64_t(ns), tf.as<uint8_t>()};
-      const uint64_t cells = (uint64_t(ns) * rps + (filter ? ns : 0)) * fbk::kSlots;
-      hipLaunchKernelGGL(fbk::k_densify_rows, dim3(uint32_t((cells + 3) / 4)), dim3(256), 0, ctx->stream, da);
-      u64* cb = dbase.as<u64>() + uint64_t(s0) * fbk::kSlots;  // (the chunk's last entry is the next chunk's first: the same number)
-      if (filter)
-        hipLaunchKernelGGL(fbk::k_bsi_cell_counts, dim3((ns * fbk::kSlots + 3) / 4), dim3(256), 0, ctx->stream, ta.as<uint8_t>(), dident.as<uint32_t>(), ns,
-                           tf.as<uint8_t>(), dfident.as<uint32_t>(), dcounts.as<uint32_t>());
-      hipLaunchKernelGGL(fbk::k_bsi_cell_scan, dim3(1), dim3(1024), 0, ctx->stream, batch->d_slots, drows.as<uint32_t>() + s0,
-                         filter ? dcounts.as<uint32_t>() : (const uint32_t*)nullptr, ns * fbk::kSlots, cb, dcur.as<u64>());
-      hipLaunchKernelGGL(fbk::k_bsi_values, dim3(ns * fbk::kSlots * bsi_values_split(ns)), dim3(256), 0, ctx->stream, ta.as<uint8_t>(), dident.as<uint32_t>(), ns,
-                         bit_depth, filter ? tf.as<uint8_t>() : (const uint8_t*)nullptr, dfident.as<uint32_t>(), dvals.as<long long>(),
-                         u64(upper), cb, d_flag, bsi_values_split(ns));
-    }
+      hipLaunchKernelGGL(fbk::k_bsi_cell_counts, dim3((ns * fbk::kSlots + 3) / 4), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, F.arena, F.rows,
+                         dcounts.as<uint32_t>());
+    hipLaunchKernelGGL(fbk::k_bsi_cell_scan, dim3(1), dim3(1024), 0, ctx->stream, batch->d_slots, ops.rows(kS, s0),
+                       filter ? dcounts.as<uint32_t>() : (const uint32_t*)nullptr, ns * fbk::kSlots, cb, dcur.as<u64>());
+    hipLaunchKernelGGL(fbk::k_bsi_values, dim3(ns * fbk::kSlots * bsi_values_split(ns)), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, bit_depth, F.arena, F.rows,
+                       dvals.as<long long>(), u64(upper), cb, d_flag, bsi_values_split(ns));
   }
   HIP_TRY(hipGetLastError());
   u64 h_cur[3] = {0, 0, 0};
@@ -1877,9 +1837,7 @@ int32_t fbk_bsi_range_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* 
   }
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  for (uint32_t s = 0; s < n_shards; ++s)
-    if (uint64_t(base_rows[s]) + 2 + bit_depth > batch->n_rows)
-      return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
   DevBuf dbase, drf, d4, dplan;
   if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
   if (filter)
@@ -1958,9 +1916,7 @@ int32_t fbk_bsi_range_between_sum(fbk_ctx* ctx, const fbk_batch* batch, const ui
   }
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  for (uint32_t s = 0; s < n_shards; ++s)
-    if (uint64_t(base_rows[s]) + 2 + bit_depth > batch->n_rows)
-      return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
   DevBuf dbase, drf, d4, dplan;
   if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
   if (filter)

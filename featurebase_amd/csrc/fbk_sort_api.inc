@@ -2,8 +2,8 @@
 // fbk_sort.hip.h.  Included by fbk.hip after fbk_extract_api.inc.
 //
 // fbk_bsi_sort walks the shards a few times (a radix-select pass per 11 key bits, a count pass, a collect pass).  A walk densifies
-// what is not dense a chunk of shards at a time, by fbk_extract_*'s rule with R = (field encoded ? bit_depth + 2 : 0) +
-// (filter encoded ? 1 : 0) rows per shard: the filter's rows first, then the field's.  Device scratch (fbk.h documents it):
+// what is not dense a chunk of shards at a time (fbk_dense_operands.inc) under fbk_extract_*'s kExtractScratch, the filter and
+// the field in a launch each.  Device scratch (fbk.h documents it):
 //   2^14 + 2^23 (histogram, the blocks' partial histograms) + 2^15 per shard (counts and prefixes of its 1024 units, key < T and
 //   key == T) + the densify chunk (<= 2^28) + 16 K (candidates) + 16 n_less + the radix sort's temporary storage (sorted pairs)
 //   + 16 n (the records) + the row lists.
@@ -11,10 +11,7 @@
 namespace {
 
 struct SortWalk {
-  const uint8_t* arenaS;
-  const uint32_t* rowsS;
-  const uint8_t* arenaF;
-  const uint32_t* rowsF;
+  DenseView S, F;  // the field, the filter
   uint32_t ns, abs0;
 };
 
@@ -31,15 +28,10 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
   *out_n = 0;
   if (out_total) *out_total = 0;
   if (flags & ~uint32_t(FBK_SORT_DESC | FBK_SORT_KEEP_ZERO)) return fail(FBK_E_INVALID, "sort: unknown flag");
-  for (uint32_t s = 0; s < n_shards; ++s) {
-    if (shard_ids[s] >= (1ull << 44)) return fail(FBK_E_INVALID, "sort: shard id >= 2^44 (column ids are shard * 2^20 + position)");
-    if (s && shard_ids[s] <= shard_ids[s - 1]) return fail(FBK_E_INVALID, "sort: shard_ids must be strictly ascending");
-  }
+  if (int32_t rc = shard_ids_ok(shard_ids, n_shards, "sort")) return rc;
   if (n_shards > (1u << 20)) return fail(FBK_E_INVALID, "sort: at most 2^20 shards per call");
   if (!ctx || !bsi || (filter && n_shards && !rows_f)) return fail(FBK_E_INVALID, "NULL argument");
-  const uint64_t rps = uint64_t(bit_depth) + 2;
-  for (uint32_t s = 0; s < n_shards; ++s)
-    if (uint64_t(base_rows[s]) + rps > bsi->n_rows) return fail(FBK_E_INVALID, "bsi: fragment rows (exists, sign, bit planes) exceed the batch");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, bsi->n_rows)) return rc;
   if (filter)
     if (int32_t rc = check_rows(rows_f, n_shards, filter->n_rows, "sort filter")) return rc;
   if (n_shards == 0) return FBK_OK;
@@ -56,37 +48,22 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
   const uint32_t passes = (nbits + fbk::kSortDigitBits - 1) / fbk::kSortDigitBits;
 
   // row lists and the densify chunk
-  const bool ds = !bsi->dense, df = filter && !filter->dense;
-  const uint32_t R = uint32_t((ds ? rps : 0) + (df ? 1 : 0));
-  const ExtractChunks ck = R ? extract_chunks(n_shards, R) : ExtractChunks{n_shards, 0};
-  const uint32_t foff = df ? ck.shards : 0;  // the field's rows follow the chunk's filter rows
-  std::vector<uint32_t> all(ds ? uint64_t(n_shards) * rps : 0), ibase(ds ? ck.shards : 0), fidx(df ? ck.shards : 0);
-  for (uint32_t s = 0; s < n_shards && ds; ++s)
-    for (uint64_t r = 0; r < rps; ++r) all[uint64_t(s) * rps + r] = uint32_t(base_rows[s] + r);
-  for (uint64_t i = 0; i < ibase.size(); ++i) ibase[i] = uint32_t(foff + i * rps);
-  for (uint64_t i = 0; i < fidx.size(); ++i) fidx[i] = uint32_t(i);
-  DevBuf rows, dense, ids, hist, part, n_lt, n_eq, p_lt, p_eq, keys, cols, skeys, scols, tmp, ocols, ovals;
-  const uint32_t* d[5];
-  if (int32_t rc = upload_rows_multi(ctx, {{base_rows, n_shards, UINT32_MAX}, {all.data(), all.size(), UINT32_MAX}, {ibase.data(), ibase.size(), UINT32_MAX},
-                                           {filter ? rows_f : nullptr, filter ? n_shards : 0, UINT32_MAX}, {fidx.data(), fidx.size(), UINT32_MAX}}, rows, d))
-    return rc;
-  if (R) HIP_TRY(dense.alloc(ctx, uint64_t(ck.shards) * R * kExtractRowBytes));
+  DenseOperands ops;
+  const int kF = ops.add(filter, rows_f, 1), kS = ops.add(bsi, base_rows, bit_depth + 2, true);
+  const uint32_t chunk = even_chunk(n_shards, kExtractScratch, kDenseRowBytes * ops.densified_rows());
+  DevBuf ids, hist, part, n_lt, n_eq, p_lt, p_eq, keys, cols, skeys, scols, tmp, ocols, ovals;
+  if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
   HIP_TRY(ids.alloc(ctx, uint64_t(n_shards) * 8));
   HIP_TRY(hipMemcpyAsync(ids.p, shard_ids, uint64_t(n_shards) * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hist.alloc(ctx, fbk::kSortBins * 8));
   HIP_TRY(part.alloc(ctx, uint64_t(fbk::kSortHistBlocks) * fbk::kSortBins * 4));
   // one walk over the shards: launch(w) per chunk, everything of the chunk dense
   auto walk = [&](auto&& launch) {
-    for (uint32_t s0 = 0; s0 < n_shards; s0 += ck.shards) {
-      const uint32_t ns = R ? std::min(ck.shards, n_shards - s0) : n_shards;
-      if (df) extract_densify(ctx, filter, d[3] + s0, ns, dense.as<uint8_t>());
-      if (ds) extract_densify(ctx, bsi, d[1] + uint64_t(s0) * rps, uint64_t(ns) * rps, dense.as<uint8_t>() + uint64_t(foff) * kExtractRowBytes);
-      SortWalk w;
-      w.arenaS = ds ? dense.as<uint8_t>() : bsi->d_arena, w.rowsS = ds ? d[2] : d[0] + s0;
-      w.arenaF = !filter ? nullptr : df ? dense.as<uint8_t>() : filter->d_arena, w.rowsF = !filter ? nullptr : df ? d[4] : d[3] + s0;
-      w.ns = ns, w.abs0 = s0;
-      launch(w, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)));
-      if (!R) break;
+    for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
+      const uint32_t ns = std::min(chunk, n_shards - s0);
+      ops.densify_one(ctx, kF, s0, ns);  // (a launch each: the filter's rows, then the field's)
+      ops.densify_one(ctx, kS, s0, ns);
+      launch(SortWalk{ops.view(kS, s0), ops.view(kF, s0), ns, s0}, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)));
     }
   };
 
@@ -99,7 +76,7 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
     HIP_TRY(hipMemsetAsync(hist.p, 0, fbk::kSortBins * 8, ctx->stream));
     walk([&](const SortWalk& w, dim3 grid) {
       const uint32_t nb = std::min(grid.x, fbk::kSortHistBlocks);
-      hipLaunchKernelGGL(fbk::k_sort_hist, dim3(nb), dim3(256), 0, ctx->stream, w.arenaS, w.rowsS, w.arenaF, w.rowsF, w.ns, bit_depth, sk, shift, u64(T),
+      hipLaunchKernelGGL(fbk::k_sort_hist, dim3(nb), dim3(256), 0, ctx->stream, w.S.arena, w.S.rows, w.F.arena, w.F.rows, w.ns, bit_depth, sk, shift, u64(T),
                          p ? 1u : 0u, part.as<uint32_t>());
       hipLaunchKernelGGL(fbk::k_sort_hist_sum, dim3(fbk::kSortBins / 256, 32), dim3(256), 0, ctx->stream, part.as<uint32_t>(), nb, hist.as<u64>());
     });
@@ -141,7 +118,7 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
   HIP_TRY(hipMemsetAsync(n_lt.as<u64>() + n_units, 0, 8, ctx->stream));
   HIP_TRY(hipMemsetAsync(n_eq.as<u64>() + n_units, 0, 8, ctx->stream));
   walk([&](const SortWalk& w, dim3 grid) {
-    hipLaunchKernelGGL(fbk::k_sort_count, grid, dim3(256), 0, ctx->stream, w.arenaS, w.rowsS, w.arenaF, w.rowsF, w.ns, w.abs0, bit_depth, sk, u64(T),
+    hipLaunchKernelGGL(fbk::k_sort_count, grid, dim3(256), 0, ctx->stream, w.S.arena, w.S.rows, w.F.arena, w.F.rows, w.ns, w.abs0, bit_depth, sk, u64(T),
                        take_all ? 1u : 0u, n_lt.as<u64>(), n_eq.as<u64>());
   });
   size_t t_scan = 0, t_sort = 0;
@@ -157,7 +134,7 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
   HIP_TRY(keys.alloc(ctx, K * 8));
   HIP_TRY(cols.alloc(ctx, K * 8));
   walk([&](const SortWalk& w, dim3 grid) {
-    hipLaunchKernelGGL(fbk::k_sort_collect, grid, dim3(256), 0, ctx->stream, w.arenaS, w.rowsS, w.arenaF, w.rowsF, w.ns, w.abs0, bit_depth, sk, u64(T),
+    hipLaunchKernelGGL(fbk::k_sort_collect, grid, dim3(256), 0, ctx->stream, w.S.arena, w.S.rows, w.F.arena, w.F.rows, w.ns, w.abs0, bit_depth, sk, u64(T),
                        take_all ? 1u : 0u, p_lt.as<u64>(), p_eq.as<u64>(), ids.as<u64>(), u64(n_less), u64(r), keys.as<u64>(), cols.as<u64>());
   });
   HIP_TRY(hipGetLastError());
@@ -188,10 +165,7 @@ int32_t fbk_extract_open_columns(fbk_ctx* ctx, const uint64_t* columns, uint64_t
   if (!out || (n && (!columns || !out_rank)) || (n_shards && !shard_ids)) return fail(FBK_E_INVALID, "NULL argument");
   *out = nullptr;
   if (n >= (1ull << 31)) return fail(FBK_E_INVALID, "extract: " + std::to_string(n) + " columns; one handle takes fewer than 2^31");
-  for (uint32_t s = 0; s < n_shards; ++s) {
-    if (shard_ids[s] >= (1ull << 44)) return fail(FBK_E_INVALID, "extract: shard id >= 2^44 (column ids are shard * 2^20 + position)");
-    if (s && shard_ids[s] <= shard_ids[s - 1]) return fail(FBK_E_INVALID, "extract: shard_ids must be strictly ascending");
-  }
+  if (int32_t rc = shard_ids_ok(shard_ids, n_shards, "extract")) return rc;
   if (!ctx) return fail(FBK_E_INVALID, "NULL argument");
   // the slot of every column in ascending order; duplicates and foreign shards are errors
   std::vector<uint32_t> order(n);
@@ -242,8 +216,7 @@ int32_t fbk_extract_open_columns(fbk_ctx* ctx, const uint64_t* columns, uint64_t
   hipLaunchKernelGGL(fbk::k_extract_scatter, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, dpos.as<u64>(), u64(n), u64(n_words), h->sel.as<u64>());
   hipLaunchKernelGGL(fbk::k_extract_scan, dim3(span), dim3(1024), 0, ctx->stream, h->sel.as<uint8_t>(), rows.as<uint32_t>(), unit_pre.as<uint32_t>(),
                      shard_tot.as<uint32_t>());
-  hipLaunchKernelGGL(fbk::k_bsi_cell_scan, dim3(1), dim3(1024), 0, ctx->stream, static_cast<const Slot*>(nullptr), static_cast<const uint32_t*>(nullptr),
-                     shard_tot.as<uint32_t>(), span, shard_base.as<u64>(), carry.as<u64>());
+  exclusive_scan_u32(ctx, shard_tot.as<uint32_t>(), span, shard_base.as<u64>(), carry.as<u64>());
   hipLaunchKernelGGL(fbk::k_extract_upre, dim3(uint32_t((su_end + 1 + 255) / 256)), dim3(256), 0, ctx->stream, unit_pre.as<uint32_t>(), shard_base.as<u64>(),
                      u64(su_end), u64(n), h->upre.as<uint32_t>());
   HIP_TRY(hipGetLastError());
