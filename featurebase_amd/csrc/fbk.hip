@@ -10,6 +10,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -35,6 +36,7 @@
 #include "fbk_matrix_distinct.hip.h"
 #include "fbk_extract.hip.h"
 #include "fbk_sort.hip.h"
+#include "fbk_quantile.hip.h"
 #include "fbk_wire_kernels.hip.h"
 
 using fbk::Slot;
@@ -1939,6 +1941,7 @@ int32_t fbk_setop(fbk_ctx* ctx, int32_t op, const fbk_batch* a, const uint32_t* 
 #include "fbk_matrix_distinct_api.inc"
 #include "fbk_extract_api.inc"
 #include "fbk_sort_api.inc"
+#include "fbk_quantile_api.inc"
 #include "fbk_prepared_api.inc"
 #include "fbk_wire_api.inc"
 #include "fbk_cache_api.inc"

@@ -18,6 +18,7 @@ FBK_E_INVALID, FBK_E_NODEVICE, FBK_E_HIP, FBK_E_NOMEM, FBK_E_CAPACITY, FBK_E_NOT
 TYPE_NIL, TYPE_ARRAY, TYPE_BITMAP, TYPE_RUN = 0, 1, 2, 3
 OP_AND, OP_OR, OP_XOR, OP_ANDNOT = 0, 1, 2, 3
 SORT_DESC, SORT_KEEP_ZERO = 1, 2
+RANK_FROM_TOP = 1 << 63
 SETOP_KEEP_BITMAP, SETOP_OPTIMIZE = 0, 1
 QUERY_ACCUMULATE = 1
 
@@ -135,6 +136,8 @@ SIGNATURES = {
     "fbk_extract_free": (C.c_int32, [_vp, _vp]),
     "fbk_extract_open_columns": (C.c_int32, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vpp, _vp]),
     "fbk_bsi_sort": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint64, _u64p, _u64p]),
+    "fbk_bsi_quantiles": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _u64p]),
+    "fbk_bsi_percentile": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_int64, _vp, C.c_uint32, _vp, _vp, _u64p]),
     "fbk_bsi_min": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fbk_bsi_max": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fbk_bsi_distinct": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),

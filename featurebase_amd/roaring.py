@@ -722,6 +722,35 @@ class Context:
         L.check(rc)
         return cols[: n.value].copy(), vals[: n.value].copy(), int(total.value)
 
+    # -- Quantiles / Percentile ----------------------------------------------------------------
+    def _quant_args(self, batch: Batch, base_rows, bit_depth: int, filt: Optional[Batch], rows_f):
+        base = np.ascontiguousarray(base_rows, dtype=np.uint32)
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        assert rf is None or rf.size == base.size
+        args = (self.h, batch.h, base.ctypes.data, bit_depth, filt.h if filt is not None else None, rf.ctypes.data if rf is not None else None, base.size)
+        return args, (base, rf)
+
+    def bsi_quantiles(self, batch: Batch, base_rows, bit_depth: int, ranks, filt: Optional[Batch] = None, rows_f=None):
+        """The values at several ranks of an int field over exists ∩ filter in one select (fbk_bsi_quantiles): with s the ascending
+        values, rank k asks for s[k] and `lib.RANK_FROM_TOP | k` for s[N-1-k].  Returns (values int64 — Base not added —, counts
+        uint64 = the columns holding exactly that value, total N).  A rank past the end gives (0, 0).  Stored zeros take part."""
+        args, keep = self._quant_args(batch, base_rows, bit_depth, filt, rows_f)
+        rk = np.ascontiguousarray(ranks, dtype=np.uint64).reshape(-1)
+        vals, cnts, total = np.zeros(rk.size, dtype=np.int64), np.zeros(rk.size, dtype=np.uint64), C.c_uint64()
+        L.check(self.lib.fbk_bsi_quantiles(*args, rk.ctypes.data, rk.size, vals.ctypes.data, cnts.ctypes.data, C.byref(total)))
+        del keep
+        return vals, cnts, int(total.value)
+
+    def bsi_percentile(self, batch: Batch, base_rows, bit_depth: int, nth, base: int = 0, filt: Optional[Batch] = None, rows_f=None):
+        """Percentile(field=, nth=, filter=) of an int field for a list of nth in one select (fbk_bsi_percentile): (values int64 —
+        `base` added —, counts uint64, total N).  counts[i] == 0: the median of nothing (N == 0)."""
+        args, keep = self._quant_args(batch, base_rows, bit_depth, filt, rows_f)
+        pn = np.ascontiguousarray(nth, dtype=np.float64).reshape(-1)
+        vals, cnts, total = np.zeros(pn.size, dtype=np.int64), np.zeros(pn.size, dtype=np.uint64), C.c_uint64()
+        L.check(self.lib.fbk_bsi_percentile(*args, base, pn.ctypes.data, pn.size, vals.ctypes.data, cnts.ctypes.data, C.byref(total)))
+        del keep
+        return vals, cnts, int(total.value)
+
     # -- GroupBy with aggregate=Sum ------------------------------------------------------------
     def _msum_args(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, filt: Optional[Batch], rows_f):
         ra = np.ascontiguousarray(rows_a, dtype=np.uint32)

@@ -59,7 +59,7 @@ extern "C" {
  *      one-process-per-GPU exchange issued by the library itself).  fbk_batch_compact refuses a batch of another context;
  *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
  *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free; fbk_bsi_sort;
- *      fbk_extract_open_columns.
+ *      fbk_extract_open_columns; fbk_bsi_quantiles; fbk_bsi_percentile.
  *   5 (round 5): + fbk_topn_partials, options topn_semantics, matrix_shadow_arena_x.  CHANGED: fbk_topn / fbk_query_topn /
  *      fbk_group_topn with 0 < n < n_a return the reference's two-pass answer by default (topn_semantics = 1; = 0 restores
  *      round 4's exact top n of fbk_topn; round 4's per-member candidate rule of fbk_group_topn is gone — it was neither);
@@ -666,6 +666,46 @@ int32_t fbk_extract_open_columns(fbk_ctx* ctx, const uint64_t* columns, uint64_t
 int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, const fbk_batch* filter,
                      const uint32_t* rows_f, const uint64_t* shard_ids, uint32_t n_shards, uint32_t flags, uint64_t offset,
                      uint64_t limit, uint64_t* out_columns, int64_t* out_values, uint64_t cap, uint64_t* out_n, uint64_t* out_total);
+
+/* ---- Quantiles and Percentile(field=, nth=, filter=) of an int field ------------------------------
+ * Both calls are ONE radix select over the bit planes (fbk_bsi_sort's walk and key: ceil((bit_depth + 1) / 11) passes, 64-bit keys
+ * for bit_depth 63 and 64) that follows SEVERAL ranks at once: pass 0 gives N, the ranks are resolved against it, every later pass
+ * counts the next digit under each live prefix.  No column id leaves the device, so there is no shard_ids argument.
+ *  - Field layout, filter == NULL, dense or encoded batches and the chunking rule are fbk_bsi_sort's (R = (field encoded ?
+ *    bit_depth + 2 : 0) + (filter encoded ? 1 : 0)); bit_depth 0..64; at most 2^20 shards per call.
+ *  - The value of a column is fbk_extract_bsi's: sign ? -magnitude : magnitude, int64 wrap-around, Base NOT added; sign and plane
+ *    bits outside exists are ignored.
+ *  - EVERY column of exists ∩ filter takes part, stored zeros included: N is the reference's
+ *    Count(Intersect(filter, Row(field != null))) (executor.go:1390-1398).  This is NOT Sort's flattenRowValues quirk (fbk_bsi_sort
+ *    drops magnitude 0 by default); it equals fbk_bsi_sort with FBK_SORT_KEEP_ZERO.
+ *  - *out_total = N, always set.  n_shards == 0 or N == 0: FBK_OK, every out_counts[i] = 0 (and out_values[i] = 0).
+ *  - Device scratch: 2^17 (histograms) + 2^26 (the blocks' partial histograms: at most 1024 blocks of 8 x 2048 counts) + chunk
+ *    (<= 2^28, 0 if both batches are dense) + 4 * (row lists) bytes.  One launch counts under at most 8 prefixes (64 KiB of LDS); a
+ *    pass with more live prefixes takes ceil(prefixes / 8) walks over the planes.  The host reads prefixes * 2048 counts per pass.
+ *  - The result does not depend on grid size, chunking or the order in which blocks run: every count is a sum of per-block counts.
+ *
+ * fbk_bsi_quantiles: with s[0 .. N) the ascending values, ranks[i] = k asks for s[k], FBK_RANK_FROM_TOP | k for s[N-1-k].
+ *   out_values[i] = that value, out_counts[i] = the participating columns holding exactly it.  k >= N: (0, 0) — "no such rank", not
+ *   an error.  Ranks may repeat and come in any order; n_ranks <= 1024, else FBK_E_INVALID.  n_ranks == 0: the count alone, one
+ *   walk over exists and filter (no plane is read).  PERCENTILE_DISC, box plots, equi-depth histograms; no reference counterpart.
+ *
+ * fbk_bsi_percentile: executePercentile (executor.go:1310-1601) for each nth[i] (n_nth <= 256; outside [0, 100] or NaN:
+ *   FBK_E_INVALID), on value + base.  With L = uint64((double(N) * nth) / 100.0) and G = uint64((double(N) * (100 - nth)) / 100.0)
+ *   (:1408-1409): G != 0 and L == 0 -> the minimum, G == 0 -> the maximum, out_counts[i] = the columns holding it (what
+ *   ValCount.Smaller / Larger accumulate, :8446, :8526); else the reference's bisection between minimum and maximum, out_counts[i]
+ *   = 1.  The bisection is REPLAYED, not searched: "leftCount > desiredLess" holds exactly when s[L] < guess and "rightCount >
+ *   desiredGreater" exactly when s[N-1-G] > guess, so the ranks 0, N-1, L and N-1-G of one select fix every step — including the
+ *   reference's quirks (it may answer a value no column holds, and it answers the last guess when the bounds cross).  N == 0:
+ *   out_counts[i] = 0 (the median of nothing is NULL, :1399-1402).  minimum + base or maximum + base outside int64: FBK_E_INVALID.
+ *   Int, and timestamp-as-integer, fields only: the decimal branch (:1466-1490) does its arithmetic in pql.Decimal and stays with
+ *   the caller. */
+#define FBK_RANK_FROM_TOP (1ull << 63)
+int32_t fbk_bsi_quantiles(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, const fbk_batch* filter,
+                          const uint32_t* rows_f, uint32_t n_shards, const uint64_t* ranks, uint32_t n_ranks, int64_t* out_values,
+                          uint64_t* out_counts, uint64_t* out_total);
+int32_t fbk_bsi_percentile(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, const fbk_batch* filter,
+                           const uint32_t* rows_f, uint32_t n_shards, int64_t base, const double* nth, uint32_t n_nth,
+                           int64_t* out_values, uint64_t* out_counts, uint64_t* out_total);
 
 /* ---- BSI (bit-sliced integers) ----------------------------------------------------------------
  * A BSI fragment of shard s occupies bit_depth+2 consecutive rows of `batch` starting at

@@ -400,10 +400,60 @@ class Executor {
   ValCount Max(const std::string& field, const Call* filter = nullptr) { return minmax(field, filter, false); }
 
   // ---- Percentile ----------------------------------------------------------------------------
-  // executePercentile, executor.go:1310-1595 (integer fields): binary search between Min and Max
-  // on Count(Row(field < x) ∩ filter) / Count(Row(field > x) ∩ filter).  Returns false for the
-  // "median of nothing is NULL" case (:1399-1402).
+  // executePercentile, executor.go:1310-1595 (integer fields).  Returns false for the "median of
+  // nothing is NULL" case (:1399-1402).  One fbk_bsi_percentile call after the filter: the device
+  // selects the four order statistics that fix the reference's bisection and the call replays it
+  // (fbk.h) — same results as PercentileBySearch below, the reference's own procedure.
   bool Percentile(const std::string& field, double nth, const Call* filter, ValCount* out) {
+    const std::vector<ValCount> r = Percentiles(field, {nth}, filter);
+    if (r[0].Count == 0) return false;
+    *out = r[0];
+    return true;
+  }
+  // Percentile for a list of nth in ONE call (one select over the planes); Count == 0: the median of nothing.
+  std::vector<ValCount> Percentiles(const std::string& field, const std::vector<double>& nth, const Call* filter = nullptr) {
+    for (double x : nth)
+      if (!(x >= 0 && x <= 100.0)) throw Error(FBK_E_INVALID, "Percentile(): invalid nth value, should be a number between 0 and 100 inclusive");
+    Scope sc(*this, {filter});
+    const Index::IntField& f = idx_.ints_.at(field);
+    const size_t n = shards().size();
+    std::vector<ValCount> out(nth.size());
+    if (n == 0 || nth.empty()) return out;
+    const std::vector<uint32_t> base = base_rows(f);
+    std::optional<RowSet> fr;
+    if (filter) fr.emplace(eval(*filter));
+    std::vector<int64_t> vals(nth.size());
+    std::vector<uint64_t> cnts(nth.size());
+    uint64_t total = 0;
+    check(fbk_bsi_percentile(idx_.ctx_, f.batch, base.data(), f.bit_depth, fr ? fr->batch() : nullptr, fr ? fr->rows().data() : nullptr, uint32_t(n), f.base,
+                             nth.data(), uint32_t(nth.size()), vals.data(), cnts.data(), &total));
+    for (size_t i = 0; i < nth.size(); ++i) out[i] = ValCount{cnts[i] ? vals[i] : 0, int64_t(cnts[i])};
+    return out;
+  }
+  // The values (Base added) at ascending ranks of exists ∩ filter, FBK_RANK_FROM_TOP | k counting from the largest, and the
+  // number of columns holding each; a rank past the end gives {0, 0}.  One fbk_bsi_quantiles call.  Stored zeros take part.
+  std::vector<ValCount> Quantiles(const std::string& field, const std::vector<uint64_t>& ranks, const Call* filter = nullptr, uint64_t* out_total = nullptr) {
+    Scope sc(*this, {filter});
+    const Index::IntField& f = idx_.ints_.at(field);
+    const size_t n = shards().size();
+    std::vector<ValCount> out(ranks.size());
+    if (out_total) *out_total = 0;
+    if (n == 0) return out;
+    const std::vector<uint32_t> base = base_rows(f);
+    std::optional<RowSet> fr;
+    if (filter) fr.emplace(eval(*filter));
+    std::vector<int64_t> vals(ranks.size());
+    std::vector<uint64_t> cnts(ranks.size());
+    uint64_t total = 0;
+    check(fbk_bsi_quantiles(idx_.ctx_, f.batch, base.data(), f.bit_depth, fr ? fr->batch() : nullptr, fr ? fr->rows().data() : nullptr, uint32_t(n),
+                            ranks.data(), uint32_t(ranks.size()), vals.data(), cnts.data(), &total));
+    if (out_total) *out_total = total;
+    for (size_t i = 0; i < ranks.size(); ++i) out[i] = ValCount{cnts[i] ? vals[i] + f.base : 0, int64_t(cnts[i])};
+    return out;
+  }
+  // The reference's procedure itself: binary search between Min and Max on Count(Row(field < x) ∩ filter) /
+  // Count(Row(field > x) ∩ filter), one or two fbk_bsi_range calls per step.  The in-tree cross-check of Percentile.
+  bool PercentileBySearch(const std::string& field, double nth, const Call* filter, ValCount* out) {
     if (nth < 0 || nth > 100.0) throw Error(FBK_E_INVALID, "Percentile(): invalid nth value, should be a number between 0 and 100 inclusive");
     Scope sc(*this, {filter});
     const Index::IntField& f = idx_.ints_.at(field);
