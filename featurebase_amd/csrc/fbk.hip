@@ -37,6 +37,7 @@
 #include "fbk_extract.hip.h"
 #include "fbk_sort.hip.h"
 #include "fbk_quantile.hip.h"
+#include "fbk_distinct_rows.hip.h"
 #include "fbk_wire_kernels.hip.h"
 
 using fbk::Slot;
@@ -1942,6 +1943,7 @@ int32_t fbk_setop(fbk_ctx* ctx, int32_t op, const fbk_batch* a, const uint32_t* 
 #include "fbk_extract_api.inc"
 #include "fbk_sort_api.inc"
 #include "fbk_quantile_api.inc"
+#include "fbk_distinct_rows_api.inc"
 #include "fbk_prepared_api.inc"
 #include "fbk_wire_api.inc"
 #include "fbk_cache_api.inc"

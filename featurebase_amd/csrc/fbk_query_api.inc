@@ -1514,16 +1514,11 @@ int32_t fbk_bsi_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_r
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 
-static int32_t bsi_minmax(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
-                          uint32_t bit_depth, uint32_t mode, const fbk_batch* filter, const uint32_t* rows_f,
-                          int64_t* out_vals, uint64_t* out_counts) {
-  FBK_ENTER(ctx);
-  if (!ctx || !batch || (n_shards && (!base_rows || !out_vals || !out_counts)) || (filter && n_shards && !rows_f))
-    return fail(FBK_E_INVALID, "NULL argument");
-  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
-  if (n_shards == 0) return FBK_OK;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
+// Min (mode 0) / Max (mode 1) per shard.  The caller holds ctx->mu, has set the device and checked the pointers; n_shards != 0.
+// Also fbk_bsi_distinct_rows' window when arithmetic does not bound it.
+static int32_t bsi_minmax_locked(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
+                                 uint32_t bit_depth, uint32_t mode, const fbk_batch* filter, const uint32_t* rows_f,
+                                 int64_t* out_vals, uint64_t* out_counts) {
   if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
   DevBuf dbase, drf, d2;
   if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
@@ -1570,6 +1565,19 @@ static int32_t bsi_minmax(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* 
     out_counts[s] = cnt;
   }
   return FBK_OK;
+}
+
+static int32_t bsi_minmax(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
+                          uint32_t bit_depth, uint32_t mode, const fbk_batch* filter, const uint32_t* rows_f,
+                          int64_t* out_vals, uint64_t* out_counts) {
+  FBK_ENTER(ctx);
+  if (!ctx || !batch || (n_shards && (!base_rows || !out_vals || !out_counts)) || (filter && n_shards && !rows_f))
+    return fail(FBK_E_INVALID, "NULL argument");
+  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (n_shards == 0) return FBK_OK;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+  return bsi_minmax_locked(ctx, batch, base_rows, n_shards, bit_depth, mode, filter, rows_f, out_vals, out_counts);
 }
 
 int32_t fbk_bsi_min(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,

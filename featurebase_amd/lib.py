@@ -141,6 +141,7 @@ SIGNATURES = {
     "fbk_bsi_min": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fbk_bsi_max": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fbk_bsi_distinct": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),
+    "fbk_bsi_distinct_rows": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_int64, _vp, _vp, C.c_uint32, C.c_uint32, _vpp, _vp, C.c_uint64, _u32p, _u32p, _vp]),
     "fbk_topk": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
     "fbk_topn": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32, _vp]),
     "fbk_batch_compact": (C.c_int32, [_vp, _vp, _vp]),

@@ -902,6 +902,29 @@ class Context:
             L.check(rc)
             return out[: n.value].copy()
 
+    def bsi_distinct_rows(self, batch: Batch, base_rows, bit_depth: int, base: int = 0, filt: Optional[Batch] = None, rows_f=None, flags: int = 0,
+                          cap: Optional[int] = None) -> Tuple[Batch, np.ndarray, np.ndarray, np.ndarray]:
+        """Distinct(filter, field=) of an int field as a device Row (fbk_bsi_distinct_rows): the columns of the result are the
+        values + `base`, Pos for v >= 0 and Neg for -v of v < 0.  Returns (batch, pos_shards, neg_shards, counts): rows
+        [0, len(pos_shards)) of the batch are Pos's shards, the next len(neg_shards) Neg's, one empty row follows; counts per row.
+        One retry with the reported size when `cap` rows were too few."""
+        rows = np.ascontiguousarray(base_rows, dtype=np.uint32)
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        assert rf is None or rf.size == rows.size
+        cap = 64 if cap is None else cap
+        h, n_pos, n_neg = C.c_void_p(), C.c_uint32(), C.c_uint32()
+        for _ in range(2):
+            ids, counts = np.zeros(max(cap, 1), dtype=np.uint64), np.zeros(max(cap, 1), dtype=np.uint64)
+            rc = self.lib.fbk_bsi_distinct_rows(self.h, batch.h, rows.ctypes.data, bit_depth, base, filt.h if filt is not None else None,
+                                                rf.ctypes.data if rf is not None else None, rows.size, flags, C.byref(h), ids.ctypes.data, cap,
+                                                C.byref(n_pos), C.byref(n_neg), counts.ctypes.data)
+            if rc != L.FBK_E_CAPACITY:
+                break
+            cap = n_pos.value + n_neg.value
+        L.check(rc)
+        n = n_pos.value + n_neg.value
+        return Batch(self, h.value), ids[: n_pos.value].copy(), ids[n_pos.value : n].copy(), counts[:n].copy()
+
     def bsi_add(self, x: Batch, rows_x, y: Batch, rows_y, flags: int = 0) -> Batch:
         """rows_x: [n_groups, depth_x], rows_y: [n_groups, depth_y] plane rows (bit i = column i);
         out rows g*(D+1)+i = plane i of x + y (roaring.Add, roaring/add.go:12)."""

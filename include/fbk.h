@@ -59,7 +59,7 @@ extern "C" {
  *      one-process-per-GPU exchange issued by the library itself).  fbk_batch_compact refuses a batch of another context;
  *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
  *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free; fbk_bsi_sort;
- *      fbk_extract_open_columns; fbk_bsi_quantiles; fbk_bsi_percentile.
+ *      fbk_extract_open_columns; fbk_bsi_quantiles; fbk_bsi_percentile; fbk_bsi_distinct_rows.
  *   5 (round 5): + fbk_topn_partials, options topn_semantics, matrix_shadow_arena_x.  CHANGED: fbk_topn / fbk_query_topn /
  *      fbk_group_topn with 0 < n < n_a return the reference's two-pass answer by default (topn_semantics = 1; = 0 restores
  *      round 4's exact top n of fbk_topn; round 4's per-member candidate rule of fbk_group_topn is gone — it was neither);
@@ -748,6 +748,40 @@ int32_t fbk_bsi_max(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_r
 int32_t fbk_bsi_distinct(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
                          uint32_t bit_depth, const fbk_batch* filter, const uint32_t* rows_f, int64_t* out_values,
                          uint64_t cap, uint64_t* out_n);
+
+/* Distinct(filter, field=f) of an int field as a ROW, the form the reference computes: executeDistinctShardBSI (executor.go:2034-2153)
+ * returns SignedRow{Neg, Pos}, two rows whose COLUMNS are the values with bsiGroup.Base added, executeDistinct unites them over the
+ * shards (:1190-1196), executeBitmapCallShard accepts Distinct as a child (:1809) and handlePreCalls (:362-449) hands r.Pos of a
+ * Distinct on another index to the outer query as a Precomputed row — a foreign-key join.  fbk_bsi_distinct is the list form (SELECT
+ * DISTINCT: 24 bytes of scratch per column, a sort, the values on the host); here no value leaves the device and nothing is sorted:
+ * setting a bit is de-duplication.
+ *  - Field layout, filter == NULL, dense or encoded batches and the chunking rule are fbk_bsi_sort's (R = (field encoded ?
+ *    bit_depth + 2 : 0) + (filter encoded ? 1 : 0)); at most 2^20 input shards; no shard_ids argument: column ids play no part.
+ *    bit_depth 0..63; 64: FBK_E_INVALID (fbk_bsi_distinct takes such a field).
+ *  - The stored value of a column is fbk_extract_bsi's (sign ? -magnitude : magnitude; sign and plane bits outside exists are
+ *    ignored; stored zeros take part); v = stored + base.  v >= 0 sets position uint64(v) of Pos, v < 0 position uint64(-v) of Neg
+ *    (:2123-2130).  Every participating column of every input shard sets its bit in the same result: the union over shards.
+ *    minimum + base or maximum + base outside int64: FBK_E_INVALID (as fbk_bsi_percentile).
+ *  - *out_batch: rows [0, n_pos) are the shards (position >> 20) of Pos that hold a bit, ascending; rows [n_pos, n_pos + n_neg)
+ *    those of Neg, ascending; row n_pos + n_neg is an EMPTY row without containers, for the caller to name where the result does
+ *    not reach a shard.  out_shard_ids[r] = the row's shard; container keys are shard * 16 + slot; out_counts[r] (may be NULL) =
+ *    the row's cardinality, recounted from the words.  flags: 0 (bitmap containers) or FBK_SETOP_OPTIMIZE (re-encoded and compacted
+ *    as by every materialising call).  The batch is the caller's (fbk_batch_free) and a valid operand of every later call.
+ *  - *out_n_pos / *out_n_neg are always set.  cap < n_pos + n_neg: FBK_E_CAPACITY, *out_batch = NULL, out_shard_ids / out_counts
+ *    untouched (the fbk_bsi_distinct convention), decided before the output arena is allocated or a bit is scattered.  n_shards == 0,
+ *    an empty filter or nothing in exists: FBK_OK, n_pos = n_neg = 0, the batch holds the one empty row.
+ *  - The positions of one sign must lie within 2^23 consecutive shards, else FBK_E_INVALID (a field of small numbers with a few
+ *    huge outliers is not a join key; fbk_bsi_distinct returns it as a list).  The window is [0, (2^bit_depth + |base|) >> 20] where
+ *    that is within 2^23, else it comes from fbk_bsi_min / _max's kernel over exists ∩ filter (with values of both signs, whose
+ *    windows would start at 0, one more walk finds each sign's smallest position if starting at 0 is too wide).
+ *  - The output arena is (n_pos + n_neg + 1) * 2^17 bytes; if it cannot be allocated: FBK_E_NOMEM, the context stays usable.
+ *    Scratch beyond it does not grow with the columns: the densify chunk (<= 2^28), two presence bitmaps (one bit per shard of the
+ *    window and sign, <= 2^20 bytes each), their word prefixes, 12 bytes per output cell (run counts, cardinalities), row lists.
+ *  - Two walks over the planes (presence of shards; scatter of bits, which reads a word before it ORs into it and issues no atomic
+ *    for a bit already set).  OR commutes: the result does not depend on grid size, chunking or the order in which blocks run. */
+int32_t fbk_bsi_distinct_rows(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, int64_t base,
+                              const fbk_batch* filter, const uint32_t* rows_f, uint32_t n_shards, uint32_t flags, fbk_batch** out_batch,
+                              uint64_t* out_shard_ids, uint64_t cap, uint32_t* out_n_pos, uint32_t* out_n_neg, uint64_t* out_counts);
 
 /* TopK / TopN: totals[i] = sum over the shards of |A[shard][i] ∩ F[shard]| (of the stored row
  * cardinalities when filter == NULL), ordered on the device by count descending and row index

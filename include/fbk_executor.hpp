@@ -12,6 +12,7 @@
 //   executeGroupBy (groupByIterator odometer)    executor.go:3918-3990, 8617-8934
 //   executeExtract (+ executeLimitCall)          executor.go:4711-5046, 1027-1100
 //   executeSort (+ Extract(Sort(...), ...))      executor.go:9321-9385, 4686-4700, 4762-4769
+//   executeDistinct as a bitmap call + handlePreCalls (joins over a foreign index)   executor.go:1170-1230, 1809, 362-449
 // Every shard of a query is evaluated in ONE device call per operator (the reference maps a
 // closure over shards, executor.go:6449); the cross-shard reduce is the same associative
 // arithmetic (sum of counts, ValCount.Add/Smaller/Larger, concatenation of row segments).
@@ -75,14 +76,29 @@ struct SortedRow {
   std::vector<int64_t> Values;
 };
 
+// Distinct's result as rows (SignedRow{Neg, Pos}, executor.go:2034-2153): the COLUMNS of Pos are the values v >= 0, those of Neg
+// the -v of the values v < 0.  Rows [0, PosShards.size()) of the batch are Pos's shards, the next NegShards.size() Neg's, EmptyRow
+// has no containers.  The batch lives on the context of the Index that made it: a SignedRows (and every Call that holds one) must
+// not outlive that Index.
+struct SignedRows {
+  std::shared_ptr<fbk_batch> batch;
+  std::vector<uint64_t> PosShards, NegShards;  // ascending
+  uint32_t EmptyRow = 0;
+  uint32_t PosRow(uint64_t shard) const {  // the row of Pos's shard, EmptyRow where Pos has none
+    auto it = std::lower_bound(PosShards.begin(), PosShards.end(), shard);
+    return it != PosShards.end() && *it == shard ? uint32_t(it - PosShards.begin()) : EmptyRow;
+  }
+};
+
 // A PQL bitmap call (the subset on the hot path).
 struct Call {
-  enum Kind { kRow, kRange, kBetween, kIntersect, kUnion, kDifference, kXor, kNot, kAll, kShift } kind = kRow;
+  enum Kind { kRow, kRange, kBetween, kIntersect, kUnion, kDifference, kXor, kNot, kAll, kShift, kPrecomputed } kind = kRow;
   std::string field;
   uint64_t row = 0;    // Row(field=row)
   int32_t op = 0;      // FBK_BSI_* for Row(field <op> value)
   int64_t value = 0, value2 = 0;
   std::vector<Call> children;
+  std::shared_ptr<const SignedRows> pre;  // Precomputed
   static Call Row(std::string f, uint64_t r) {
     Call c;
     c.kind = kRow;
@@ -122,6 +138,14 @@ struct Call {
     c.kind = kShift;
     c.value = n;
     c.children.push_back(std::move(child));
+    return c;
+  }
+  // A Distinct evaluated beforehand, possibly on another index, as a leaf: row = r.Pos (handlePreCalls, executor.go:428-429).  It
+  // evaluates to Pos on the evaluating index's shards, to the empty row where Pos has none.
+  static Call Precomputed(const SignedRows& r) {
+    Call c;
+    c.kind = kPrecomputed;
+    c.pre = std::make_shared<const SignedRows>(r);
     return c;
   }
   bool ContainsShift() const {
@@ -178,6 +202,9 @@ class RowSet {
 class Index {
  public:
   explicit Index(int device = 0) { check(fbk_open(device, 0, &ctx_)); }
+  // A second index on a fork of `root`'s context (fbk_ctx_fork): the two share batches, so a call on one may name rows the other
+  // computed (Call::Precomputed).  It is closed before `root`.
+  explicit Index(Index& root) { check(fbk_ctx_fork(root.ctx_, &ctx_)); }
   ~Index() {
     for (auto& kv : sets_) fbk_batch_free(ctx_, kv.second.batch);
     for (auto& kv : ints_) fbk_batch_free(ctx_, kv.second.batch);
@@ -531,6 +558,73 @@ class Executor {
     return out;
   }
 
+  // Distinct(field=int field, filter) as a bitmap call: SignedRow{Neg, Pos} left on the device (fbk_bsi_distinct_rows), the operand
+  // of a join (Call::Precomputed).  A field whose values span more shards of a row than the call takes (or of bit depth 64) goes
+  // through Distinct() and an upload instead.
+  SignedRows DistinctRows(const std::string& field, const Call* filter = nullptr) {
+    Scope sc(*this, {filter});
+    const Index::IntField& f = idx_.ints_.at(field);
+    const size_t n = shards().size();
+    std::vector<uint32_t> base = base_rows(f);
+    std::optional<RowSet> fr;
+    if (filter) fr.emplace(eval(*filter));
+    SignedRows out;
+    fbk_batch* b = nullptr;
+    uint32_t n_pos = 0, n_neg = 0;
+    std::vector<uint64_t> ids(64);
+    for (;;) {
+      const int32_t rc = fbk_bsi_distinct_rows(idx_.ctx_, f.batch, base.data(), f.bit_depth, f.base, fr ? fr->batch() : nullptr, fr ? fr->rows().data() : nullptr,
+                                               uint32_t(n), FBK_SETOP_OPTIMIZE, &b, ids.data(), ids.size(), &n_pos, &n_neg, nullptr);
+      if (rc == FBK_E_CAPACITY) {
+        ids.assign(size_t(n_pos) + n_neg, 0);
+        continue;
+      }
+      if (rc == FBK_E_INVALID && std::string(fbk_last_error(nullptr)).find("fbk_bsi_distinct") != std::string::npos) {  // (the message names the way out)
+        b = nullptr;
+        break;
+      }
+      check(rc);
+      break;
+    }
+    if (!b) {
+      std::map<uint64_t, std::vector<uint64_t>> by_shard[2];  // Pos, Neg
+      for (int64_t v : Distinct(field, filter)) {
+        const uint64_t p = v < 0 ? 0 - uint64_t(v) : uint64_t(v);
+        by_shard[v < 0][p / ShardWidth].push_back(p % ShardWidth);
+      }
+      std::vector<fbk_container_desc> descs;
+      std::vector<uint8_t> payload;
+      ids.clear();
+      for (auto& sign : by_shard)
+        for (auto& sc2 : sign) {
+          Index::append_row(sc2.second, sc2.first * 16, uint32_t(ids.size()), descs, payload);
+          ids.push_back(sc2.first);
+        }
+      n_pos = uint32_t(by_shard[0].size()), n_neg = uint32_t(by_shard[1].size());
+      if (payload.empty()) payload.push_back(0);
+      check(fbk_batch_upload(idx_.ctx_, descs.data(), descs.size(), n_pos + n_neg + 1, payload.data(), payload.size(), &b));
+    }
+    fbk_ctx* ctx = idx_.ctx_;
+    out.batch = std::shared_ptr<fbk_batch>(b, [ctx](fbk_batch* x) { fbk_batch_free(ctx, x); });
+    out.PosShards.assign(ids.begin(), ids.begin() + n_pos);
+    out.NegShards.assign(ids.begin() + n_pos, ids.begin() + n_pos + n_neg);
+    out.EmptyRow = n_pos + n_neg;
+    return out;
+  }
+  // the values a DistinctRows result stands for, ascending (Neg's columns negated): what Distinct() lists
+  std::vector<int64_t> Values(const SignedRows& r) {
+    std::vector<int64_t> out;
+    const size_t n_pos = r.PosShards.size(), n = n_pos + r.NegShards.size();
+    if (n == 0) return out;
+    std::vector<uint32_t> rows(n);
+    for (size_t i = 0; i < n; ++i) rows[i] = uint32_t(i);
+    for_each_bit(r.batch.get(), rows, [&](uint32_t i, uint64_t p) {
+      out.push_back(i < n_pos ? int64_t(r.PosShards[i] * ShardWidth + p) : int64_t(0 - (r.NegShards[i - n_pos] * ShardWidth + p)));
+    });
+    std::sort(out.begin(), out.end());
+    return out;
+  }
+
   // ---- TopK / TopN ---------------------------------------------------------------------------
   // TopK(field, k, filter): per-row |row ∩ filter| over all shards (doTopK), then the rows in
   // descending count order, ascending id inside one count, zero counts dropped
@@ -826,6 +920,12 @@ class Executor {
       case Call::kRange:
       case Call::kBetween: return range(c);
       case Call::kAll: return leaf_row(Index::kExistence, 0);
+      case Call::kPrecomputed: {
+        if (!c.pre || !c.pre->batch) throw Error(FBK_E_INVALID, "Precomputed() without a result");
+        std::vector<uint32_t> rows;
+        for (uint64_t s : shards()) rows.push_back(c.pre->PosRow(s));
+        return RowSet(idx_.ctx_, c.pre->batch.get(), std::move(rows), false);
+      }
       case Call::kShift: {
         if (c.children.size() != 1) throw Error(FBK_E_INVALID, c.children.empty() ? "Shift() requires an input row" : "Shift() only accepts a single row input");
         if (c.value < 0) throw Error(FBK_E_INVALID, "cannot shift by negative values");  // row.go:375-377
@@ -864,10 +964,12 @@ class Executor {
     for (uint64_t c : counts) n += c;
     return n;
   }
-  std::vector<uint64_t> columns(const RowSet& r) {
-    // gather the result rows into one batch, download, expand
+  // fn(i, p) for every set bit of rows[i]: p = its position within the shard row
+  template <class Fn>
+  void for_each_bit(const fbk_batch* b, const std::vector<uint32_t>& rows, Fn&& fn) {
+    // gather the rows into one batch, download, expand
     fbk_batch* o = nullptr;
-    check(fbk_setop(idx_.ctx_, FBK_OP_OR, r.batch(), r.rows().data(), r.batch(), r.rows().data(), r.rows().size(), 0, &o, nullptr));
+    check(fbk_setop(idx_.ctx_, FBK_OP_OR, b, rows.data(), b, rows.data(), rows.size(), 0, &o, nullptr));
     uint32_t n_rows = 0;
     uint64_t nc = 0, pb = 0;
     check(fbk_batch_info(idx_.ctx_, o, &n_rows, &nc, &pb));
@@ -876,14 +978,17 @@ class Executor {
     int32_t rc = fbk_batch_download(idx_.ctx_, o, descs.data(), nc, payload.data(), pb);
     fbk_batch_free(idx_.ctx_, o);
     check(rc);
-    std::vector<uint64_t> out;
     for (uint64_t i = 0; i < nc; ++i) {
       const fbk_container_desc& d = descs[i];
-      const uint64_t hb = (shards()[d.row] * 16 + (d.key & 15)) << 16;
+      const uint64_t hb = (d.key & 15) << 16;
       const uint64_t* w = reinterpret_cast<const uint64_t*>(payload.data() + d.off);  // keep-bitmap output: 1024 words
       for (uint32_t k = 0; k < FBK_BITMAP_WORDS; ++k)
-        for (uint64_t x = w[k]; x; x &= x - 1) out.push_back(hb | (uint64_t(k) * 64 + uint64_t(__builtin_ctzll(x))));
+        for (uint64_t x = w[k]; x; x &= x - 1) fn(d.row, hb | (uint64_t(k) * 64 + uint64_t(__builtin_ctzll(x))));
     }
+  }
+  std::vector<uint64_t> columns(const RowSet& r) {
+    std::vector<uint64_t> out;
+    for_each_bit(r.batch(), r.rows(), [&](uint32_t i, uint64_t p) { out.push_back(shards()[i] * ShardWidth + p); });
     std::sort(out.begin(), out.end());
     return out;
   }
