@@ -32,12 +32,23 @@ def _order_key(vals: np.ndarray, desc: bool) -> np.ndarray:
 def brute(S: np.ndarray, F: Optional[np.ndarray], shard_ids: Sequence[int], depth: int, desc: bool = False, keep_zero: bool = False, offset: int = 0,
           limit: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, int]:
     """S [n_shards, depth + 2, 16, 1024], F [n_shards, 16, 1024] or None -> (columns uint64[n], values int64[n], total)"""
+    return order(*records(S, F, shard_ids, depth), desc, keep_zero, offset, limit)
+
+
+def records(S: np.ndarray, F: Optional[np.ndarray], shard_ids: Sequence[int], depth: int) -> Tuple[np.ndarray, np.ndarray]:
+    """brute()'s first half: (columns uint64, values int64) of exists ∩ filter in ascending column order, stored zeros included"""
     if S.shape[0] == 0:
-        return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.int64), 0
+        return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.int64)
     consider = S[:, 0] if F is None else S[:, 0] & F
     sh, pos, cols = X.select(consider, shard_ids)
     vals, pres = X.bsi_expected(S, depth, sh, pos)
     assert pres.all()
+    return cols, vals
+
+
+def order(cols: np.ndarray, vals: np.ndarray, desc: bool = False, keep_zero: bool = False, offset: int = 0,
+          limit: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """brute()'s second half, for callers that order one list of records several ways"""
     if not keep_zero:
         cols, vals = cols[vals != 0], vals[vals != 0]  # value 0 <=> magnitude 0 (the negation of a non-zero magnitude below 2^64 is not 0)
     order = np.lexsort((cols, _order_key(vals, desc)))

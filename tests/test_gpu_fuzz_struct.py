@@ -3,7 +3,13 @@
 of the hot path — compared with set algebra on the oracle containers' bit content (the per-container semantics are
 pinned elsewhere: golden tables, test_gpu_parity.py; this file goes after indexing, scheduling and path-selection
 bugs; tests/test_gpu_fuzz.py is the chained-operation fuzz).  FBK_FUZZ_ITERS=<n> runs more iterations, FBK_TEST_SEED
-re-rolls them (scripts/fuzz_parity.sh)."""
+re-rolls them (scripts/fuzz_parity.sh).
+
+The rest of the entry points are fuzzed in
+  tests/test_gpu_fuzz_ops.py  the calls that read densified operands: Sort, Extract, Quantiles / Percentile, GroupBy Sum and
+                              Count(Distinct), Distinct rows; and their walks with a shorter last chunk
+  tests/fuzz_ops_gen.py       its case generator and expectations (no GPU)
+  tests/test_fuzz_ops_cpu.py  the generator and the references checked against each other (no GPU)"""
 import os
 
 import numpy as np
