@@ -1875,6 +1875,7 @@ int32_t fbk_plan_detach_output(fbk_ctx* ctx, fbk_plan* plan, fbk_batch** out_bat
   std::lock_guard<std::mutex> g(ctx->mu);
   if (!plan->out) return fail(FBK_E_INVALID, "plan has no set-op output yet");
   *out_batch = plan->out;
+  plan->out->borrowed = false;  // the caller's from here on: nothing rewrites it in place any more (fbk_batch_compact accepts it)
   plan->out = nullptr;
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)

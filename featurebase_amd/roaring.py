@@ -193,6 +193,12 @@ class Plan:
         L.check(self.ctx.lib.fbk_plan_output(self.ctx.h, self.h, C.byref(h)))
         return Batch(self.ctx, h.value)
 
+    def detach_output(self) -> Batch:
+        """The plan's set-op output handed to the caller, who frees it; the plan's next setop makes a fresh one."""
+        h = C.c_void_p()
+        L.check(self.ctx.lib.fbk_plan_detach_output(self.ctx.h, self.h, C.byref(h)))
+        return Batch(self.ctx, h.value)
+
     def free(self) -> None:
         if self.h:
             L.check(self.ctx.lib.fbk_plan_free(self.ctx.h, self.h))

@@ -329,3 +329,35 @@ def test_prepared_row_records_follow_a_rewritten_batch(gpu_ctx, mixed):
         gpu_ctx.set_option("matrix_fused", -1)
     batch.free()
     F.free()
+
+
+def test_detached_plan_output_belongs_to_the_caller(gpu_ctx, mixed):
+    """fbk_plan_detach_output hands the set-op output over: the plan's next set-op writes a fresh batch and leaves the detached one
+    alone, and the detached batch is an owned batch like any other — fbk_batch_compact, which refuses the borrowed outputs of plans
+    and prepared queries, moves it into a right-sized arena (found by tests/test_gpu_fuzz_prepared.py: it used to be refused)."""
+    rows, g, filt, OA, OF = mixed
+    batch = gpu_ctx.upload_flat(rows.descs(), rows.payload(), rows.n_rows)
+    ia, ib = g[:, :4].reshape(-1), g[:, 4:8].reshape(-1)
+    plan = gpu_ctx.plan(batch, ia, batch, ib)
+    plan.setop(L.OP_AND, L.SETOP_OPTIMIZE)
+    with pytest.raises(L.FbkError):
+        plan.output().compact()  # borrowed: the plan's next run rewrites it in place
+    EA, ca = PB.setop(PB.OP_AND, OA, ia, OA, ib)
+    d = plan.detach_output()
+    with pytest.raises(L.FbkError):
+        plan.output()  # nothing to lend until the next set-op
+    plan.setop(L.OP_XOR)
+    EX, cx = PB.setop(PB.OP_XOR, OA, ia, OA, ib)
+    assert plan.output().h.value != d.h.value
+    assert (_words_of(plan.output()) == EX.words()).all() and (plan.read() == cx).all()
+    assert (_words_of(d) == EA.words()).all() and (d.count(np.arange(len(ia))) == ca).all()
+    before = d.memory()[0]
+    assert before == len(ia) * 16 * 8192
+    after = d.compact()
+    assert after < before and after == d.memory()[0]
+    assert (_words_of(d) == EA.words()).all()
+    plan.setop(L.OP_OR)  # and again after the compaction: still the caller's rows
+    assert (_words_of(d) == EA.words()).all()
+    plan.free()
+    d.free()
+    batch.free()
