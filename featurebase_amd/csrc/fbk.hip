@@ -141,7 +141,7 @@ struct FbkOptions {
   int64_t ring_geom = 0;                 // k_icount3's block: 0 = 10 decoders + 64 KiB ring, one block per CU; 1 = 8 decoders; 2 = 6 decoders; 3 = 5 decoders + 32 KiB ring, two blocks per CU
   int64_t ring_nt = 0;                   //   1: the payload DMAs carry the non-temporal hint
   int64_t ring_flags = 0;                //   experiments on k_icount3 (bit 0: ring space is released after the decode)
-  int64_t ring_debug = 0;                //   1: every block reports the cycles its loader and decoders spent waiting; the averages go to stderr after each launch (which is then synchronous)#endif
+  int64_t ring_debug = 0;                //   1: every block reports the cycles its loader and decoders spent waiting; the averages go to stderr after each launch (which is then synchronous)
 #endif
 };
 
@@ -1381,6 +1381,8 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 
 }  // extern "C"
 
+#include "fbk_output.inc"
+
 struct fbk_plan {
   fbk_ctx* ctx = nullptr;
   const fbk_batch* a = nullptr;
@@ -1404,9 +1406,6 @@ struct fbk_plan {
 };
 
 namespace {
-
-int32_t optimize_cells(fbk_ctx* ctx, fbk_batch* o, const uint32_t* d_runs);  // fbk_query_api.inc
-int32_t compact_cells(fbk_ctx* ctx, fbk_batch* o);                            // fbk_query_api.inc
 
 // Average encoded payload per container of a batch, in bytes.
 uint64_t batch_avg_payload(const fbk_batch* b) {
@@ -1509,16 +1508,6 @@ void launch_setop(bool dense, fbk_plan* p, hipStream_t st, bool want_runs, const
     hipLaunchKernelGGL(fbk::k_setop<OP>, dim3(blocks), dim3(256), 0, st, p->a->d_slots, p->a->d_arena, p->d_rows_a,
                        p->b->d_slots, p->b->d_arena, p->d_rows_b, p->n_pairs, p->out->d_arena, p->out->d_slots,
                        want_runs ? p->d_runs : nullptr, direct);
-}
-
-void free_batch_storage(fbk_batch* b) {
-  if (!b) return;
-  if (b->d_arena) (void)ctx_free(b->ctx, b->d_arena);
-  if (b->d_slots) (void)ctx_free(b->ctx, b->d_slots);
-  if (b->d_win) (void)ctx_free(b->ctx, b->d_win);
-  if (b->d_shadow_arena) (void)ctx_free(b->ctx, b->d_shadow_arena);
-  if (b->d_shadow_slots) (void)ctx_free(b->ctx, b->d_shadow_slots);
-  delete b;
 }
 
 void free_plan_storage(fbk_plan* p) {
@@ -1714,14 +1703,9 @@ int32_t plan_setop_enqueue_locked(fbk_ctx* ctx, fbk_plan* p, int32_t op, bool wa
     // itself the output of an asynchronous operation
     if (int32_t rc = refresh_slots(const_cast<fbk_batch*>(p->a))) return rc;
     if (int32_t rc = refresh_slots(const_cast<fbk_batch*>(p->b))) return rc;
-    fbk_batch* o = new (std::nothrow) fbk_batch();
-    if (!o) return fail(FBK_E_NOMEM, "host allocation failed");
-    o->ctx = ctx;
-    o->n_rows = uint32_t(p->n_pairs);
-    o->arena_bytes = n_slots * 8192ull;
-    o->ring_regular = true;  // (8 KiB cells)
-    o->h_slots.assign(n_slots, Slot{0, 0, 0});
-    o->h_keys.assign(n_slots, 0);
+    if (int32_t rc = alloc_cell_batch(ctx, p->n_pairs, &p->out, "setop output")) return rc;
+    fbk_batch* o = p->out;
+    o->borrowed = true;
     for (uint64_t i = 0; i < p->n_pairs; ++i)
       for (int s = 0; s < fbk::kSlots; ++s) {
         const uint64_t ia = uint64_t(p->h_rows_a[i]) * fbk::kSlots + s, ib = uint64_t(p->h_rows_b[i]) * fbk::kSlots + s;
@@ -1729,15 +1713,6 @@ int32_t plan_setop_enqueue_locked(fbk_ctx* ctx, fbk_plan* p, int32_t op, bool wa
         const bool has_a = fbk::slot_type(p->a->h_slots[ia]) != fbk::kTypeNil;
         o->h_keys[i * fbk::kSlots + s] = has_a ? p->a->h_keys[ia] : p->b->h_keys[ib];
       }
-    hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&o->d_arena), std::max<uint64_t>(o->arena_bytes, 16));
-    if (e == hipSuccess) e = ctx_malloc(ctx, reinterpret_cast<void**>(&o->d_slots), std::max<uint64_t>(n_slots, 1) * sizeof(Slot));
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      free_batch_storage(o);
-      return fail(e == hipErrorOutOfMemory ? FBK_E_NOMEM : FBK_E_HIP, std::string("setop output: ") + hipGetErrorString(e));
-    }
-    p->out = o;
-    o->borrowed = true;
   }
   if (want_runs && !p->d_runs) HIP_TRY(ctx_malloc(ctx, reinterpret_cast<void**>(&p->d_runs), std::max<uint64_t>(n_slots, 1) * 4));
   if (p->n_pairs == 0) return FBK_OK;

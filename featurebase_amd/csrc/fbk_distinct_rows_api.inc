@@ -41,7 +41,7 @@ int32_t fbk_bsi_distinct_rows(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t
   DenseOperands ops;
   const int kF = ops.add(filter, rows_f, 1), kS = ops.add(bsi, base_rows, bit_depth + 2, true);
   const uint32_t chunk = n_shards ? even_chunk(n_shards, kExtractScratch, kDenseRowBytes * ops.densified_rows()) : 1;
-  DevBuf pres, pre, druns, dcnt, inner;
+  DevBuf pres, pre, inner;
   auto walk = [&](auto&& launch) {
     for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
       const uint32_t ns = std::min(chunk, n_shards - s0);
@@ -133,8 +133,9 @@ int32_t fbk_bsi_distinct_rows(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t
   const uint64_t n = n_sign[0] + n_sign[1];
   *out_n_pos = uint32_t(n_sign[0]), *out_n_neg = uint32_t(n_sign[1]);
   if (n > cap) return fail(FBK_E_CAPACITY, "distinct rows: " + std::to_string(n) + " rows, capacity " + std::to_string(cap));
-  fbk_batch* o = nullptr;
-  if (int32_t rc = alloc_cell_batch(ctx, n + 1, &o)) return rc;
+  CellOutput out;  // (declared after hpre, the source of a copy: a failure drains the stream before hpre goes)
+  if (int32_t rc = out.alloc(ctx, n + 1, n + 1, "distinct rows")) return rc;
+  fbk_batch* o = out.batch();
   {
     uint64_t r = 0;
     for (uint32_t sg = 0; sg < 2; ++sg)
@@ -148,32 +149,19 @@ int32_t fbk_bsi_distinct_rows(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t
 
   // 4. scatter, 5. the cells' descriptors, cardinalities and run counts; then the common tail of the materialising calls
   const uint32_t n_cells = uint32_t((n + 1) * fbk::kSlots);
-  int32_t rc = FBK_OK;
-  hipError_t e = hipMemsetAsync(o->d_arena, 0, o->arena_bytes, ctx->stream);
-  if (e == hipSuccess) e = druns.alloc(ctx, uint64_t(n_cells) * 4);
-  if (e == hipSuccess) e = dcnt.alloc(ctx, (n + 1) * 8);
-  if (e == hipSuccess) e = hipMemsetAsync(dcnt.p, 0, (n + 1) * 8, ctx->stream);
-  if (e == hipSuccess && n) e = pre.alloc(ctx, uint64_t(n_words) * 4);
-  if (e == hipSuccess && n) e = hipMemcpyAsync(pre.p, hpre.data(), uint64_t(n_words) * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    rc = fail(e == hipErrorOutOfMemory ? FBK_E_NOMEM : FBK_E_HIP, std::string("distinct rows: ") + hipGetErrorString(e));
+  HIP_TRY(hipMemsetAsync(o->d_arena, 0, o->arena_bytes, ctx->stream));
+  if (n) {
+    HIP_TRY(pre.alloc(ctx, uint64_t(n_words) * 4));
+    HIP_TRY(hipMemcpyAsync(pre.p, hpre.data(), uint64_t(n_words) * 4, hipMemcpyHostToDevice, ctx->stream));
+    walk([&](const DenseView& S, const DenseView& F, uint32_t ns, dim3 grid) {
+      hipLaunchKernelGGL(fbk::k_drow_scatter, grid, dim3(256), 0, ctx->stream, S.arena, S.rows, F.arena, F.rows, ns, bit_depth, u64(base), win,
+                         pres.as<u64>(), pre.as<uint32_t>(), uint32_t(n_sign[0]), uint32_t(n), reinterpret_cast<u64*>(o->d_arena));
+    });
   }
-  if (!rc) {
-    if (n)
-      walk([&](const DenseView& S, const DenseView& F, uint32_t ns, dim3 grid) {
-        hipLaunchKernelGGL(fbk::k_drow_scatter, grid, dim3(256), 0, ctx->stream, S.arena, S.rows, F.arena, F.rows, ns, bit_depth, u64(base), win,
-                           pres.as<u64>(), pre.as<uint32_t>(), uint32_t(n_sign[0]), uint32_t(n), reinterpret_cast<u64*>(o->d_arena));
-      });
-    hipLaunchKernelGGL(fbk::k_drow_finish, dim3((n_cells + 3) / 4), dim3(256), 0, ctx->stream, o->d_arena, n_cells, o->d_slots, druns.as<uint32_t>(), dcnt.as<u64>());
-    rc = finish_output(ctx, o, flags, druns.as<uint32_t>(), dcnt.as<u64>(), n, out_counts);
-  }
+  hipLaunchKernelGGL(fbk::k_drow_finish, dim3((n_cells + 3) / 4), dim3(256), 0, ctx->stream, o->d_arena, n_cells, o->d_slots, out.runs(), out.counts());
+  if (int32_t rc = out.finish(flags, n, out_counts)) return rc;
   (void)hipStreamSynchronize(ctx->stream);  // (hpre is the source of a copy)
-  if (rc) {
-    free_batch_storage(o);
-    return rc;
-  }
-  *out_batch = o;
+  *out_batch = out.release();
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 

@@ -241,15 +241,7 @@ int32_t fbk_query_bsi_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t
   if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
   if (n_shards == 0) return fail(FBK_E_INVALID, "query: no shards");
   BsiProg prog;
-  switch (op) {  // rangeOp, fragment.go:937-950
-    case FBK_BSI_EQ: gen_eq(prog, bit_depth, predicate); break;
-    case FBK_BSI_NEQ: gen_neq(prog, bit_depth, predicate); break;
-    case FBK_BSI_LT: gen_lt(prog, bit_depth, predicate, false); break;
-    case FBK_BSI_LTE: gen_lt(prog, bit_depth, predicate, true); break;
-    case FBK_BSI_GT: gen_gt(prog, bit_depth, predicate, false); break;
-    case FBK_BSI_GTE: gen_gt(prog, bit_depth, predicate, true); break;
-    default: return fail(FBK_E_INVALID, "invalid range operation");  // ErrInvalidRangeOperation
-  }
+  if (!gen_range_op(prog, op, bit_depth, predicate)) return fail(FBK_E_INVALID, "invalid range operation");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
   if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;

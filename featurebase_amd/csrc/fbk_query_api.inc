@@ -1,152 +1,9 @@
 // fbk_query_api.inc — host side of the query-level entry points (included by fbk.hip).
-// n-way union, count matrix (GroupBy/TopK), BSI Sum/Range, and the optimize() re-encode
-// pass shared by every materialising operation.
+// n-way fold, count matrix (GroupBy / TopK / TopN), Rows, Flip, Shift, and the BSI calls: Range, Sum / Min / Max and the range
+// sums (one frame: BsiShardOperands + download_words), Add, Distinct.  The output batch of the materialising ones is a
+// CellOutput (fbk_output.inc).
 
 namespace {
-
-// Output batch in "cell" layout: one 8 KiB bitmap cell per (row, slot).
-int32_t alloc_cell_batch(fbk_ctx* ctx, uint64_t n_rows, fbk_batch** out) {
-  const uint64_t n_slots = n_rows * fbk::kSlots;
-  fbk_batch* o = new (std::nothrow) fbk_batch();
-  if (!o) return fail(FBK_E_NOMEM, "host allocation failed");
-  o->ctx = ctx;
-  o->n_rows = uint32_t(n_rows);
-  o->arena_bytes = n_slots * 8192ull;
-  o->ring_regular = true;  // (8 KiB cells)
-  o->h_slots.assign(n_slots, Slot{0, 0, 0});
-  o->h_keys.assign(n_slots, 0);
-  // default keys: out_row * 16 + slot, the fragment-storage form (rowID << 4 | slot) with the output
-  // row ordinal standing for the row / shard id — unique and ascending in (row, slot) order, so the
-  // batch serialises (fbk_batch_download_roaring); fold / shift overwrite them with the keys they
-  // carry through from their inputs
-  for (uint64_t s = 0; s < n_slots; ++s) o->h_keys[s] = s;
-  hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&o->d_arena), std::max<uint64_t>(o->arena_bytes, 16));
-  if (e == hipSuccess) e = ctx_malloc(ctx, reinterpret_cast<void**>(&o->d_slots), std::max<uint64_t>(n_slots, 1) * sizeof(Slot));
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    free_batch_storage(o);
-    return fail(e == hipErrorOutOfMemory ? FBK_E_NOMEM : FBK_E_HIP, std::string("output batch: ") + hipGetErrorString(e));
-  }
-  *out = o;
-  return FBK_OK;
-}
-
-// Container.optimize() for every cell of `o` (roaring.go:3412-3461): re-encode into a
-// right-sized arena.  d_runs holds the run count of every cell (bitmapCountRuns).
-int32_t optimize_cells(fbk_ctx* ctx, fbk_batch* o, const uint32_t* d_runs) {
-  const uint64_t n_slots = uint64_t(o->n_rows) * fbk::kSlots;
-  if (n_slots == 0) return FBK_OK;
-  DevBuf dtype, dbytes, doff, dblk, dblkoff, dtotal;
-  const uint64_t n_blk = (n_slots + 1023) / 1024;
-  HIP_TRY(dtype.alloc(ctx, n_slots * 4));
-  HIP_TRY(dbytes.alloc(ctx, n_slots * 8));
-  HIP_TRY(doff.alloc(ctx, n_slots * 8));
-  HIP_TRY(dblk.alloc(ctx, n_blk * 8));
-  HIP_TRY(dblkoff.alloc(ctx, n_blk * 8));
-  HIP_TRY(dtotal.alloc(ctx, 8));
-  hipLaunchKernelGGL(fbk::k_encode_plan, dim3(uint32_t((n_slots + 255) / 256)), dim3(256), 0, ctx->stream, o->d_slots,
-                     d_runs, n_slots, dtype.as<uint32_t>(), dbytes.as<u64>());
-  hipLaunchKernelGGL(fbk::k_scan_blocks, dim3(uint32_t(n_blk)), dim3(1024), 0, ctx->stream, dbytes.as<u64>(), doff.as<u64>(), n_slots,
-                     dblk.as<u64>());
-  hipLaunchKernelGGL(fbk::k_exclusive_scan, dim3(1), dim3(1024), 0, ctx->stream, dblk.as<u64>(), dblkoff.as<u64>(), n_blk,
-                     dtotal.as<u64>());
-  HIP_TRY(hipGetLastError());
-  u64 total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, dtotal.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  uint8_t* d_new = nullptr;
-  Slot* d_new_slots = nullptr;
-  HIP_TRY(ctx_malloc(ctx, reinterpret_cast<void**>(&d_new), std::max<u64>(total, 16)));
-  hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&d_new_slots), n_slots * sizeof(Slot));
-  if (e != hipSuccess) {
-    (void)ctx_free(ctx, d_new);
-    return fail(FBK_E_NOMEM, "optimize: slot table allocation failed");
-  }
-  hipLaunchKernelGGL(fbk::k_encode_write, dim3(uint32_t((n_slots + 3) / 4)), dim3(256), 0, ctx->stream, o->d_slots,
-                     o->d_arena, dtype.as<uint32_t>(), doff.as<u64>(), dblkoff.as<u64>(), d_runs, n_slots, d_new, d_new_slots);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    (void)ctx_free(ctx, d_new);
-    (void)ctx_free(ctx, d_new_slots);
-    return fail(FBK_E_HIP, std::string("optimize: ") + hipGetErrorString(e));
-  }
-  (void)ctx_free(o->ctx, o->d_arena);
-  (void)ctx_free(o->ctx, o->d_slots);
-  o->d_arena = d_new;
-  o->d_slots = d_new_slots;
-  o->arena_bytes = total;
-  o->dense = false;
-  slots_rewritten(o);
-  return FBK_OK;
-}
-
-// The containers of `o` are in their final encodings but live at the head of 8 KiB cells (a kernel applied optimize() itself):
-// move them into a right-sized arena — the payload sizes, the scan and one copy per container, nothing is decoded.  A batch that is
-// handed to the caller (fragment cache, long-lived rows) then holds what round 3's separate re-encode pass left it with, not
-// n_rows x 16 x 8 KiB.  No-op when nothing would be saved.
-int32_t compact_cells(fbk_ctx* ctx, fbk_batch* o) {
-  const uint64_t n_slots = uint64_t(o->n_rows) * fbk::kSlots;
-  if (n_slots == 0) return FBK_OK;
-  DevBuf dbytes, doff, dblk, dblkoff, dtotal;
-  const uint64_t n_blk = (n_slots + 1023) / 1024;
-  HIP_TRY(dbytes.alloc(ctx, n_slots * 8));
-  HIP_TRY(doff.alloc(ctx, n_slots * 8));
-  HIP_TRY(dblk.alloc(ctx, n_blk * 8));
-  HIP_TRY(dblkoff.alloc(ctx, n_blk * 8));
-  HIP_TRY(dtotal.alloc(ctx, 8));
-  hipLaunchKernelGGL(fbk::k_compact_plan, dim3(uint32_t((n_slots + 255) / 256)), dim3(256), 0, ctx->stream, o->d_slots, n_slots, dbytes.as<u64>());
-  hipLaunchKernelGGL(fbk::k_scan_blocks, dim3(uint32_t(n_blk)), dim3(1024), 0, ctx->stream, dbytes.as<u64>(), doff.as<u64>(), n_slots, dblk.as<u64>());
-  hipLaunchKernelGGL(fbk::k_exclusive_scan, dim3(1), dim3(1024), 0, ctx->stream, dblk.as<u64>(), dblkoff.as<u64>(), n_blk, dtotal.as<u64>());
-  HIP_TRY(hipGetLastError());
-  u64 total = 0;
-  HIP_TRY(hipMemcpyAsync(&total, dtotal.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (total + (1u << 20) >= o->arena_bytes) return FBK_OK;  // (nothing worth a copy)
-  uint8_t* d_new = nullptr;
-  Slot* d_new_slots = nullptr;
-  HIP_TRY(ctx_malloc(ctx, reinterpret_cast<void**>(&d_new), std::max<u64>(total, 16)));
-  hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&d_new_slots), n_slots * sizeof(Slot));
-  if (e != hipSuccess) {
-    (void)ctx_free(ctx, d_new);
-    return fail(FBK_E_NOMEM, "compact: slot table allocation failed");
-  }
-  hipLaunchKernelGGL(fbk::k_compact_write, dim3(uint32_t((n_slots + 3) / 4)), dim3(256), 0, ctx->stream, o->d_slots, o->d_arena, dbytes.as<u64>(), doff.as<u64>(),
-                     dblkoff.as<u64>(), n_slots, d_new, d_new_slots);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    (void)ctx_free(ctx, d_new);
-    (void)ctx_free(ctx, d_new_slots);
-    return fail(FBK_E_HIP, std::string("compact: ") + hipGetErrorString(e));
-  }
-  (void)ctx_free(o->ctx, o->d_arena);
-  (void)ctx_free(o->ctx, o->d_slots);
-  o->d_arena = d_new;
-  o->d_slots = d_new_slots;
-  o->arena_bytes = total;
-  o->dense = false;
-  slots_rewritten(o);
-  return FBK_OK;
-}
-
-// Common tail of a materialising op: optional optimize(), refresh host slots, counts D2H.
-int32_t finish_output(fbk_ctx* ctx, fbk_batch* o, uint32_t flags, const uint32_t* d_runs, const u64* d_counts,
-                      uint64_t n_counts, uint64_t* out_counts, bool encoded_in_cells = false) {
-  HIP_TRY(hipGetLastError());
-  if (out_counts && n_counts)
-    HIP_TRY(hipMemcpyAsync(out_counts, d_counts, n_counts * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-  slots_rewritten(o);
-  if (flags & FBK_SETOP_OPTIMIZE) {
-    if (int32_t rc = optimize_cells(ctx, o, d_runs)) return rc;
-  } else if (encoded_in_cells && ctx->opt.setop_compact) {
-    // the kernel applied optimize() itself: the caller OWNS this batch from here on, give it a right-sized arena
-    if (int32_t rc = compact_cells(ctx, o)) return rc;
-  }
-  if (int32_t rc = refresh_slots(o)) return rc;
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return FBK_OK;
-}
 
 int32_t check_rows(const uint32_t* rows, uint64_t n, uint32_t limit, const char* what) {
   for (uint64_t i = 0; i < n; ++i)
@@ -469,52 +326,61 @@ bool plan_between_sum(uint64_t depth, int64_t lo, int64_t hi, fbk::BetweenSumPla
   return true;
 }
 
+// rangeOp, fragment.go:937-950.  false: not a range operation (ErrInvalidRangeOperation)
+bool gen_range_op(BsiProg& p, int32_t op, uint32_t depth, int64_t predicate) {
+  switch (op) {
+    case FBK_BSI_EQ: gen_eq(p, depth, predicate); break;
+    case FBK_BSI_NEQ: gen_neq(p, depth, predicate); break;
+    case FBK_BSI_LT: gen_lt(p, depth, predicate, false); break;
+    case FBK_BSI_LTE: gen_lt(p, depth, predicate, true); break;
+    case FBK_BSI_GT: gen_gt(p, depth, predicate, false); break;
+    case FBK_BSI_GTE: gen_gt(p, depth, predicate, true); break;
+    default: return false;
+  }
+  return true;
+}
+
+// The filter operand of a launch: its descriptors, its arena and its row list on the device; no filter: all NULL.
+struct FilterArgs {
+  const Slot* slots = nullptr;
+  const uint8_t* arena = nullptr;
+  const uint32_t* rows = nullptr;
+  FilterArgs(const fbk_batch* filter, const uint32_t* d_rows) {
+    if (filter) slots = filter->d_slots, arena = filter->d_arena, rows = d_rows;
+  }
+};
+
 int32_t run_bsi_program(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint64_t n_shards,
                         uint64_t bit_depth, const BsiProg& prog, uint32_t flags, fbk_batch** out_batch,
                         uint64_t* out_counts) {
   if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
-  fbk_batch* o = nullptr;
-  if (int32_t rc = alloc_cell_batch(ctx, n_shards, &o)) return rc;
-  DevBuf dbase, dprog, druns, dcnt;
-  int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase);
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    e = dprog.alloc(ctx, std::max<size_t>(prog.v.size(), 1) * 4);
-    if (e == hipSuccess && !prog.v.empty())
-      e = hipMemcpyAsync(dprog.p, prog.v.data(), prog.v.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = druns.alloc(ctx, std::max<uint64_t>(n_shards * fbk::kSlots, 1) * 4);
-    if (e == hipSuccess) e = dcnt.alloc(ctx, std::max<uint64_t>(n_shards, 1) * 8);
-    if (e == hipSuccess && n_shards) e = hipMemsetAsync(dcnt.p, 0, n_shards * 8, ctx->stream);
-    if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("bsi range: ") + hipGetErrorString(e));
+  DevBuf dbase, dprog;
+  CellOutput out;
+  if (int32_t rc = out.alloc(ctx, n_shards, n_shards, "bsi range")) return rc;
+  if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
+  hipError_t e = dprog.alloc(ctx, std::max<size_t>(prog.v.size(), 1) * 4);
+  if (e == hipSuccess && !prog.v.empty())
+    e = hipMemcpyAsync(dprog.p, prog.v.data(), prog.v.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? FBK_E_NOMEM : FBK_E_HIP, std::string("bsi range: ") + hipGetErrorString(e));
   }
   // optimize() asked for: applied by the kernel itself (option setop_direct_encode = 2; otherwise the separate re-encode pass)
   const bool enc = (flags & FBK_SETOP_OPTIMIZE) && ctx->opt.setop_direct_encode == 2;
-  if (!rc && n_shards) {
+  if (n_shards) {
     {
       KernelSpan span(ctx);
       // one wavefront per (shard, slot)
       hipLaunchKernelGGL(fbk::k_bsi_range_slot, dim3(uint32_t(n_shards * fbk::kSlots)), dim3(64), 0, ctx->stream,
                          batch->d_slots, batch->d_arena, dbase.as<uint32_t>(), uint32_t(n_shards), dprog.as<uint32_t>(),
-                         uint32_t(prog.v.size()), uint32_t(bit_depth + 2), o->d_arena, o->d_slots, druns.as<uint32_t>(), dcnt.as<u64>(), uint32_t(enc));
+                         uint32_t(prog.v.size()), uint32_t(bit_depth + 2), out.batch()->d_arena, out.batch()->d_slots, out.runs(), out.counts(), uint32_t(enc));
     }
-    rc = finish_output(ctx, o, enc ? (flags & ~uint32_t(FBK_SETOP_OPTIMIZE)) : flags, druns.as<uint32_t>(), dcnt.as<u64>(), n_shards, out_counts, enc != 0);
+    if (int32_t rc = out.finish(enc ? (flags & ~uint32_t(FBK_SETOP_OPTIMIZE)) : flags, n_shards, out_counts, enc)) return rc;
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (rc) {
-    free_batch_storage(o);
-    return rc;
-  }
-  *out_batch = o;
+  *out_batch = out.release();
   return FBK_OK;
 }
-
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
 
 template <int WRITE>  // 0 counts only, 1 bitmap cells (+ run counts), 2 Container.optimize() in the kernel's epilogue
 void launch_fold(int32_t op, uint32_t blocks, hipStream_t st, const Slot* slots, const uint8_t* arena, const uint32_t* rows,
@@ -538,18 +404,28 @@ void launch_fold(int32_t op, uint32_t blocks, hipStream_t st, const Slot* slots,
 #undef FBK_FOLD
 }
 
-// output keys of a fold: high bits of the first container found in the group's first row
+// The key rule of the materialising row operations: an output row's keys are (high | slot), high = the high key bits of the
+// first non-nil container of its source row.  false: the row has no container.
+bool row_key_high(const fbk_batch* batch, uint32_t row, uint64_t* high) {
+  for (int s = 0; s < fbk::kSlots; ++s) {
+    const uint64_t is = uint64_t(row) * fbk::kSlots + s;
+    if (fbk::slot_type(batch->h_slots[is]) != fbk::kTypeNil) {
+      *high = batch->h_keys[is] & ~15ull;
+      return true;
+    }
+  }
+  return false;
+}
+void set_row_keys(fbk_batch* o, uint64_t row, uint64_t high) {
+  for (int s = 0; s < fbk::kSlots; ++s) o->h_keys[row * fbk::kSlots + s] = high | uint64_t(s);
+}
+
+// output keys of a fold: those of the group's first row (a row without containers: 0)
 void fold_output_keys(const fbk_batch* batch, const uint32_t* rows, uint64_t n_groups, uint32_t k, fbk_batch* o) {
   for (uint64_t gi = 0; gi < n_groups && k; ++gi) {
     uint64_t high = 0;
-    for (int s = 0; s < fbk::kSlots; ++s) {
-      const uint64_t is = uint64_t(rows[gi * k]) * fbk::kSlots + s;
-      if (fbk::slot_type(batch->h_slots[is]) != fbk::kTypeNil) {
-        high = batch->h_keys[is] & ~15ull;
-        break;
-      }
-    }
-    for (int s = 0; s < fbk::kSlots; ++s) o->h_keys[gi * fbk::kSlots + s] = high | uint64_t(s);
+    (void)row_key_high(batch, rows[gi * k], &high);
+    set_row_keys(o, gi, high);
   }
 }
 
@@ -557,43 +433,32 @@ int32_t fold_n_locked(fbk_ctx* ctx, int32_t op, const fbk_batch* batch, const ui
                       uint32_t flags, fbk_batch** out_batch, uint64_t* out_counts) {
   if (int32_t rc = check_rows(rows, n_groups * k, batch->n_rows, "fold_n")) return rc;
   if (int32_t rc = refresh_slots(const_cast<fbk_batch*>(batch))) return rc;  // h_slots / h_keys of an asynchronously produced input
-  fbk_batch* o = nullptr;
-  if (int32_t rc = alloc_cell_batch(ctx, n_groups, &o)) return rc;
+  DevBuf drows;
+  CellOutput out;
+  if (int32_t rc = out.alloc(ctx, n_groups, n_groups, "fold_n")) return rc;
+  fbk_batch* o = out.batch();
   fold_output_keys(batch, rows, n_groups, k, o);
-  DevBuf drows, druns, dcnt;
-  int32_t rc = upload_rows(ctx, rows, n_groups * k, batch->n_rows, drows);
-  if (!rc) {
-    hipError_t e = druns.alloc(ctx, std::max<uint64_t>(n_groups * fbk::kSlots, 1) * 4);
-    if (e == hipSuccess) e = dcnt.alloc(ctx, std::max<uint64_t>(n_groups, 1) * 8);
-    if (e == hipSuccess && n_groups) e = hipMemsetAsync(dcnt.p, 0, n_groups * 8, ctx->stream);
-    if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("fold_n: ") + hipGetErrorString(e));
-  }
-  if (!rc && n_groups) {
-    bool encoded_in_cells = false;
+  if (int32_t rc = upload_rows(ctx, rows, n_groups * k, batch->n_rows, drows)) return rc;
+  if (n_groups) {
+    // optimize() asked for: the fold kernels encode in their epilogue (the register-accumulating kernel — n-way Intersect —
+    // from wave 0's fragment)
+    const bool enc = (flags & FBK_SETOP_OPTIMIZE) != 0;
     {
       KernelSpan span(ctx);
-      // optimize() asked for: the fold kernels encode in their epilogue (the register-accumulating kernel — n-way Intersect —
-      // from wave 0's fragment)
-      const bool enc = (flags & FBK_SETOP_OPTIMIZE) != 0;
       if (enc) {
         launch_fold<2>(op, uint32_t(n_groups * fbk::kSlots), ctx->stream, batch->d_slots, batch->d_arena, drows.as<uint32_t>(), n_groups, k, nullptr, nullptr,
-                       nullptr, o->d_arena, o->d_slots, nullptr, dcnt.as<u64>());
+                       nullptr, o->d_arena, o->d_slots, nullptr, out.counts());
         flags &= ~uint32_t(FBK_SETOP_OPTIMIZE);
         o->dense = false;
-        encoded_in_cells = true;
       } else {
         launch_fold<1>(op, uint32_t(n_groups * fbk::kSlots), ctx->stream, batch->d_slots, batch->d_arena, drows.as<uint32_t>(), n_groups, k, nullptr, nullptr,
-                       nullptr, o->d_arena, o->d_slots, druns.as<uint32_t>(), dcnt.as<u64>());
+                       nullptr, o->d_arena, o->d_slots, out.runs(), out.counts());
       }
     }
-    rc = finish_output(ctx, o, flags, druns.as<uint32_t>(), dcnt.as<u64>(), n_groups, out_counts, encoded_in_cells);
+    if (int32_t rc = out.finish(flags, n_groups, out_counts, enc)) return rc;
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (rc) {
-    free_batch_storage(o);
-    return rc;
-  }
-  *out_batch = o;
+  *out_batch = out.release();
   return FBK_OK;
 }
 
@@ -607,11 +472,11 @@ int32_t fold_n_icount_upload_rows(fbk_ctx* ctx, const fbk_batch* batch, const ui
 int32_t fold_n_icount_launch(fbk_ctx* ctx, int32_t op, const fbk_batch* batch, const uint32_t* const* dr, uint64_t n_groups, uint32_t k,
                              const fbk_batch* filter, u64* d_counts, bool accumulate, const Slot* recs = nullptr) {
   if (!accumulate) HIP_TRY(hipMemsetAsync(d_counts, 0, n_groups * 8, ctx->stream));
+  const FilterArgs f(filter, dr[1]);
   {
     KernelSpan span(ctx);
     launch_fold<0>(op, uint32_t(n_groups * fbk::kSlots), ctx->stream, batch->d_slots, batch->d_arena, dr[0], n_groups, k,
-                       filter ? filter->d_slots : nullptr, filter ? filter->d_arena : nullptr, filter ? dr[1] : nullptr, nullptr, nullptr,
-                       nullptr, d_counts, recs);
+                       f.slots, f.arena, f.rows, nullptr, nullptr, nullptr, d_counts, recs);
   }
   HIP_TRY(hipGetLastError());
   return FBK_OK;
@@ -877,6 +742,7 @@ int32_t count_matrix_enqueue_locked(fbk_ctx* ctx, const fbk_batch* a, const uint
     const uint32_t* ra = dra + uint64_t(p0) * n_a;
     const uint32_t* rb = drb + uint64_t(p0) * n_b;
     const uint32_t* rf = filter ? drf + p0 : nullptr;
+    const FilterArgs f(filter, rf);
     u64* d_out = dshard.as<u64>();
     HIP_TRY(hipMemsetAsync(d_out, 0, uint64_t(pn) * width * 8, ctx->stream));
     {
@@ -893,7 +759,7 @@ int32_t count_matrix_enqueue_locked(fbk_ctx* ctx, const fbk_batch* a, const uint
     } else if (a->dense && b->dense && (!filter || filter->dense) && n_b > 1) {
       // every container a bitmap at a fixed address: the matrix-core kernel (fbk_matrix_mfma.hip.h)
       launch_matrix_dense(ctx, a->d_arena, ra, n_a, b->d_arena, rb, n_b,
-                          filter ? filter->d_arena : (const uint8_t*)nullptr, rf, pn, d_out);
+                          f.arena, rf, pn, d_out);
     } else if (n_b > 1 && fused_mode != 0 && (fused_mode == 1 || matrix_prefers_fused(n_a, n_b))) {
       // array / run containers among the rows: decoded inside the matrix-core kernel, a stage of 8192
       // bit positions at a time (fbk_matrix_fused.hip.h) — the encoded payload is the only HBM traffic
@@ -926,7 +792,7 @@ int32_t count_matrix_enqueue_locked(fbk_ctx* ctx, const fbk_batch* a, const uint
         if (filter)
           if (int32_t rc = window_index(ctx, filter, &wf)) return rc;
         // heavy containers (runs, long arrays) as dense shadows, built per batch on first use (option matrix_shadow)
-        const Slot *sla = a->d_slots, *slb = b->d_slots, *slf = filter ? filter->d_slots : nullptr;
+        const Slot *sla = a->d_slots, *slb = b->d_slots, *slf = f.slots;
         bool sha = false, shb = false, shf = false;
         if (int32_t rc = heavy_shadow(ctx, a, &sla, &sha)) return rc;
         if (int32_t rc = heavy_shadow(ctx, b, &slb, &shb)) return rc;
@@ -988,9 +854,7 @@ int32_t count_matrix_enqueue_locked(fbk_ctx* ctx, const fbk_batch* a, const uint
       for (uint32_t j0 = 0; j0 < n_b; j0 += 256) {
         const uint32_t nbc = std::min<uint32_t>(256, n_b - j0);
         hipLaunchKernelGGL(fbk::k_count_matrix<TA>, dim3(blocks), dim3(512), 0, ctx->stream, a->d_slots, a->d_arena,
-                           ra, n_a, b->d_slots, b->d_arena, rb, n_b, j0, nbc,
-                           filter ? filter->d_slots : (const Slot*)nullptr, filter ? filter->d_arena : (const uint8_t*)nullptr,
-                           rf, pn, spb, d_out);
+                           ra, n_a, b->d_slots, b->d_arena, rb, n_b, j0, nbc, f.slots, f.arena, rf, pn, spb, d_out);
       }
     }
     }
@@ -1286,7 +1150,7 @@ int32_t fbk_topk_bsi(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, u
   *out_depth = 0;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  DevBuf dtot, dmax, druns;
+  DevBuf dtot, dmax;
   HIP_TRY(dtot.alloc(ctx, std::max<uint64_t>(n_a, 1) * 8));
   HIP_TRY(dmax.alloc(ctx, 8));
   HIP_TRY(hipMemsetAsync(dmax.p, 0, 8, ctx->stream));
@@ -1301,27 +1165,18 @@ int32_t fbk_topk_bsi(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, u
   }
   const uint32_t depth = uint32_t(bits_len64(mx));  // planes the largest count needs (bsiBuilder grows the same way, bsi.go:256)
   *out_depth = depth;
-  fbk_batch* o = nullptr;
-  if (int32_t rc = alloc_cell_batch(ctx, depth, &o)) return rc;
-  int32_t rc = FBK_OK;
+  CellOutput out;
+  if (int32_t rc = out.alloc(ctx, depth, 0, "topk_bsi")) return rc;
   if (depth) {
+    fbk_batch* o = out.batch();
     const uint64_t n_slots = uint64_t(depth) * fbk::kSlots;
-    hipError_t e = druns.alloc(ctx, n_slots * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(o->d_arena, 0, n_slots * 8192ull, ctx->stream);
-    if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("topk_bsi: ") + hipGetErrorString(e));
-    if (!rc) {
-      hipLaunchKernelGGL(fbk::k_counts_to_bsi, dim3((n_a + 255) / 256), dim3(256), 0, ctx->stream, dtot.as<u64>(), n_a, depth, o->d_arena);
-      hipLaunchKernelGGL(fbk::k_cell_stats, dim3(uint32_t((n_slots + 3) / 4)), dim3(256), 0, ctx->stream, o->d_arena, o->d_slots,
-                         druns.as<uint32_t>(), n_slots);
-      rc = finish_output(ctx, o, flags, druns.as<uint32_t>(), nullptr, 0, nullptr);
-    }
+    HIP_TRY(hipMemsetAsync(o->d_arena, 0, n_slots * 8192ull, ctx->stream));
+    hipLaunchKernelGGL(fbk::k_counts_to_bsi, dim3((n_a + 255) / 256), dim3(256), 0, ctx->stream, dtot.as<u64>(), n_a, depth, o->d_arena);
+    hipLaunchKernelGGL(fbk::k_cell_stats, dim3(uint32_t((n_slots + 3) / 4)), dim3(256), 0, ctx->stream, o->d_arena, o->d_slots, out.runs(), n_slots);
+    if (int32_t rc = out.finish(flags, 0, nullptr)) return rc;
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (rc) {
-    free_batch_storage(o);
-    return rc;
-  }
-  *out_batch = o;
+  *out_batch = out.release();
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 
@@ -1404,57 +1259,100 @@ int32_t fbk_flip(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* rows, uin
   fbk_batch* bb = const_cast<fbk_batch*>(batch);
   if (int32_t rc = refresh_slots(bb)) return rc;
   if (int32_t rc = check_rows(rows, n_rows, batch->n_rows, "flip")) return rc;
-  fbk_batch* o = nullptr;
-  if (int32_t rc = alloc_cell_batch(ctx, n_rows, &o)) return rc;
+  DevBuf drows;
+  CellOutput out;
+  if (int32_t rc = out.alloc(ctx, n_rows, n_rows, "flip")) return rc;
+  fbk_batch* o = out.batch();
   for (uint64_t i = 0; i < n_rows; ++i) {  // keys: those of the flipped row (a row without containers: row ordinal << 4)
     uint64_t high = i << 4;
-    for (int sl = 0; sl < fbk::kSlots; ++sl) {
-      const uint64_t is = uint64_t(rows[i]) * fbk::kSlots + sl;
-      if (fbk::slot_type(batch->h_slots[is]) != fbk::kTypeNil) {
-        high = batch->h_keys[is] & ~15ull;
-        break;
-      }
-    }
-    for (int sl = 0; sl < fbk::kSlots; ++sl) o->h_keys[i * fbk::kSlots + sl] = high | uint64_t(sl);
+    (void)row_key_high(batch, rows[i], &high);
+    set_row_keys(o, i, high);
   }
-  DevBuf drows, druns, dcnt;
-  int32_t rc = upload_rows(ctx, rows, n_rows, UINT32_MAX, drows);
-  if (!rc) {
-    hipError_t e = druns.alloc(ctx, std::max<uint64_t>(n_rows * fbk::kSlots, 1) * 4);
-    if (e == hipSuccess) e = dcnt.alloc(ctx, std::max<uint64_t>(n_rows, 1) * 8);
-    if (e == hipSuccess && n_rows) e = hipMemsetAsync(dcnt.p, 0, n_rows * 8, ctx->stream);
-    if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("flip: ") + hipGetErrorString(e));
-  }
+  if (int32_t rc = upload_rows(ctx, rows, n_rows, UINT32_MAX, drows)) return rc;
   const bool enc = (flags & FBK_SETOP_OPTIMIZE) && ctx->opt.setop_direct_encode == 2;  // optimize() inside the kernel
-  if (!rc && n_rows) {
+  if (n_rows) {
     hipLaunchKernelGGL(fbk::k_flip, dim3(uint32_t((n_rows * fbk::kSlots + 3) / 4)), dim3(256), 0, ctx->stream, batch->d_slots, batch->d_arena,
-                       drows.as<uint32_t>(), n_rows, uint32_t(start), uint32_t(end), o->d_arena, o->d_slots, druns.as<uint32_t>(), dcnt.as<u64>(), uint32_t(enc));
-    rc = finish_output(ctx, o, enc ? (flags & ~uint32_t(FBK_SETOP_OPTIMIZE)) : flags, druns.as<uint32_t>(), dcnt.as<u64>(), n_rows, out_counts, enc != 0);
+                       drows.as<uint32_t>(), n_rows, uint32_t(start), uint32_t(end), o->d_arena, o->d_slots, out.runs(), out.counts(), uint32_t(enc));
+    if (int32_t rc = out.finish(enc ? (flags & ~uint32_t(FBK_SETOP_OPTIMIZE)) : flags, n_rows, out_counts, enc)) return rc;
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (rc) {
-    free_batch_storage(o);
-    return rc;
-  }
-  *out_batch = o;
+  *out_batch = out.release();
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
-
 
 }  // extern "C"
 
 namespace {
 
+// ---- the per-shard BSI aggregates (Sum, Min / Max, the range sums): one frame ------------------------------------------
+// check the arguments, take the lock, upload the operands (BsiShardOperands), launch into W words per shard, download them
+// (download_words), fold them on the host.
+
+// pointers and depth; the outputs may be NULL only without shards (then the call returns FBK_OK right after this)
+int32_t bsi_aggregate_args_ok(const fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards, uint32_t bit_depth,
+                              const fbk_batch* filter, const uint32_t* rows_f, const void* out_a, const void* out_b) {
+  if (!ctx || !batch || (n_shards && (!base_rows || !out_a || !out_b)) || (filter && n_shards && !rows_f))
+    return fail(FBK_E_INVALID, "NULL argument");
+  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  return FBK_OK;
+}
+
+// base_rows and the filter's rows on the device (two copies, in this order).  The caller holds ctx->mu and has set the device.
+struct BsiShardOperands {
+  DevBuf dbase, drf;
+  int32_t upload(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards, uint32_t bit_depth, const fbk_batch* filter,
+                 const uint32_t* rows_f) {
+    if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
+    if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
+    if (filter)
+      if (int32_t rc = upload_rows(ctx, rows_f, n_shards, filter->n_rows, drf)) return rc;
+    return FBK_OK;
+  }
+  const uint32_t* base() { return dbase.as<uint32_t>(); }
+  const uint32_t* filter_rows() { return drf.as<uint32_t>(); }  // NULL without a filter
+};
+
+// the words a launch left in `d`, on the host once this returns (one synchronisation)
+int32_t download_words(fbk_ctx* ctx, DevBuf& d, uint64_t n_words, std::vector<u64>& h) {
+  h.resize(n_words);
+  D2H back(ctx);
+  HIP_TRY(back.add(h.data(), d.p, n_words * 8));
+  HIP_TRY(back.finish());
+  return FBK_OK;
+}
+
+// The two-pass form of a range sum, the reference's own two steps: the range as a Row (`rng`, owned from here on: freed on every
+// path), then fragment.sum with that Row (∩ the caller's filter) as the filter.  Called WITHOUT the context's lock: the public
+// entry points used here take it themselves.
+int32_t bsi_sum_over_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards, uint32_t bit_depth, fbk_batch* rng,
+                           const fbk_batch* filter, const uint32_t* rows_f, int64_t* out_sums, uint64_t* out_counts) {
+  struct Owned {
+    fbk_ctx* ctx;
+    fbk_batch* b;
+    ~Owned() { (void)fbk_batch_free(ctx, b); }
+  } row{ctx, rng};
+  std::vector<uint32_t> ident(n_shards);
+  for (uint32_t s = 0; s < n_shards; ++s) ident[s] = s;
+  if (filter) {
+    fbk_batch* both = nullptr;
+    const int32_t rc = fbk_setop(ctx, FBK_OP_AND, row.b, ident.data(), filter, rows_f, n_shards, 0, &both, nullptr);
+    (void)fbk_batch_free(ctx, row.b);
+    row.b = both;  // (NULL after a failure)
+    if (rc) return rc;
+  }
+  return fbk_bsi_sum(ctx, batch, base_rows, n_shards, bit_depth, row.b, ident.data(), out_sums, out_counts);
+}
+
 // launch only: d3[s] = {psum, nsum, count} of shard s (zeroed here)
 int32_t bsi_sum_launch(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* d_base, uint32_t n_shards, uint32_t bit_depth, const fbk_batch* filter,
                        const uint32_t* d_rf, u64* d3) {
   HIP_TRY(hipMemsetAsync(d3, 0, uint64_t(n_shards) * 24, ctx->stream));
+  const FilterArgs f(filter, d_rf);
   {
     KernelSpan span(ctx);
     // one wavefront per (shard, slot)
     hipLaunchKernelGGL(fbk::k_bsi_sum_slot, dim3(uint32_t(uint64_t(n_shards) * fbk::kSlots)), dim3(64), 0, ctx->stream,
-                       batch->d_slots, batch->d_arena, d_base, n_shards, bit_depth,
-                       filter ? filter->d_slots : (const Slot*)nullptr, filter ? filter->d_arena : (const uint8_t*)nullptr, d_rf, d3);
+                       batch->d_slots, batch->d_arena, d_base, n_shards, bit_depth, f.slots, f.arena, d_rf, d3);
   }
   HIP_TRY(hipGetLastError());
   return FBK_OK;
@@ -1465,16 +1363,17 @@ int32_t bsi_sum_launch(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* d_b
 int32_t bsi_range_sum_launch(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* d_base, uint32_t n_shards, const fbk::RangeSumPlan& pl,
                              const fbk::RangeSumPlan* d_plan, const fbk_batch* filter, const uint32_t* d_rf, u64* d4) {
   HIP_TRY(hipMemsetAsync(d4, 0, uint64_t(n_shards) * 32, ctx->stream));
+  const FilterArgs f(filter, d_rf);
   {
     KernelSpan span(ctx);
     if (batch->dense) {  // half a container per wavefront, three planes in flight (four measured equal in round 3 and were dropped in round 5)
       auto kern = pl.take_other ? fbk::k_bsi_range_sum_half<true, 3> : fbk::k_bsi_range_sum_half<false, 3>;
       hipLaunchKernelGGL(kern, dim3(uint32_t(uint64_t(n_shards) * fbk::kSlots * 2)), dim3(64), 0, ctx->stream, batch->d_arena, d_base, n_shards, d_plan,
-                         filter ? filter->d_slots : (const Slot*)nullptr, filter ? filter->d_arena : (const uint8_t*)nullptr, d_rf, d4);
+                         f.slots, f.arena, d_rf, d4);
     } else {
       auto kern = pl.take_other ? fbk::k_bsi_range_sum_slot<true> : fbk::k_bsi_range_sum_slot<false>;
       hipLaunchKernelGGL(kern, dim3(uint32_t(uint64_t(n_shards) * fbk::kSlots)), dim3(64), 0, ctx->stream, batch->d_slots, batch->d_arena, d_base,
-                         n_shards, d_plan, filter ? filter->d_slots : (const Slot*)nullptr, filter ? filter->d_arena : (const uint8_t*)nullptr, d_rf, d4);
+                         n_shards, d_plan, f.slots, f.arena, d_rf, d4);
     }
   }
   HIP_TRY(hipGetLastError());
@@ -1489,23 +1388,17 @@ int32_t fbk_bsi_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_r
                     uint32_t bit_depth, const fbk_batch* filter, const uint32_t* rows_f, int64_t* out_sums,
                     uint64_t* out_counts) try {
   FBK_ENTER(ctx);
-  if (!ctx || !batch || (n_shards && (!base_rows || !out_sums || !out_counts)) || (filter && n_shards && !rows_f))
-    return fail(FBK_E_INVALID, "NULL argument");
-  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (int32_t rc = bsi_aggregate_args_ok(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f, out_sums, out_counts)) return rc;
   if (n_shards == 0) return FBK_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
-  DevBuf dbase, drf, d3;
-  if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
-  if (filter)
-    if (int32_t rc = upload_rows(ctx, rows_f, n_shards, filter->n_rows, drf)) return rc;
+  BsiShardOperands ops;
+  if (int32_t rc = ops.upload(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f)) return rc;
+  DevBuf d3;
   HIP_TRY(d3.alloc(ctx, uint64_t(n_shards) * 24));
-  if (int32_t rc = bsi_sum_launch(ctx, batch, dbase.as<uint32_t>(), n_shards, bit_depth, filter, drf.as<uint32_t>(), d3.as<u64>())) return rc;
-  std::vector<u64> h3(uint64_t(n_shards) * 3);
-  D2H back(ctx);
-  HIP_TRY(back.add(h3.data(), d3.p, h3.size() * 8));
-  HIP_TRY(back.finish());
+  if (int32_t rc = bsi_sum_launch(ctx, batch, ops.base(), n_shards, bit_depth, filter, ops.filter_rows(), d3.as<u64>())) return rc;
+  std::vector<u64> h3;
+  if (int32_t rc = download_words(ctx, d3, uint64_t(n_shards) * 3, h3)) return rc;
   for (uint32_t s = 0; s < n_shards; ++s) {
     // Total(): int64(psum) - int64(nsum) (roaring/filter.go:1106-1108)
     out_sums[s] = int64_t(uint64_t(h3[s * 3 + 0]) - uint64_t(h3[s * 3 + 1]));
@@ -1519,26 +1412,22 @@ int32_t fbk_bsi_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_r
 static int32_t bsi_minmax_locked(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
                                  uint32_t bit_depth, uint32_t mode, const fbk_batch* filter, const uint32_t* rows_f,
                                  int64_t* out_vals, uint64_t* out_counts) {
-  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
-  DevBuf dbase, drf, d2;
-  if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
-  if (filter)
-    if (int32_t rc = upload_rows(ctx, rows_f, n_shards, filter->n_rows, drf)) return rc;
+  BsiShardOperands ops;
+  if (int32_t rc = ops.upload(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f)) return rc;
   // one wavefront per (shard, slot), folded per shard on the host: min over a shard = the smallest of
   // its slots' minima, its count = the sum over the slots that reach it (max alike)
   const uint64_t n_out = uint64_t(n_shards) * fbk::kSlots;
+  DevBuf d2;
   HIP_TRY(d2.alloc(ctx, n_out * 16));
+  const FilterArgs f(filter, ops.filter_rows());
   {
     KernelSpan span(ctx);
     hipLaunchKernelGGL(fbk::k_bsi_minmax_slot, dim3(uint32_t(n_out)), dim3(64), 0, ctx->stream, batch->d_slots, batch->d_arena,
-                       dbase.as<uint32_t>(), n_shards, bit_depth, mode, filter ? filter->d_slots : (const Slot*)nullptr,
-                       filter ? filter->d_arena : (const uint8_t*)nullptr, drf.as<uint32_t>(), d2.as<u64>());
+                       ops.base(), n_shards, bit_depth, mode, f.slots, f.arena, f.rows, d2.as<u64>());
   }
   HIP_TRY(hipGetLastError());
-  std::vector<u64> h2(n_out * 2);
-  D2H back(ctx);
-  HIP_TRY(back.add(h2.data(), d2.p, h2.size() * 8));
-  HIP_TRY(back.finish());
+  std::vector<u64> h2;
+  if (int32_t rc = download_words(ctx, d2, n_out * 2, h2)) return rc;
   for (uint32_t s = 0; s < n_shards; ++s) {
     // fragment.min (fragment.go:754-779): negatives present => -(maxUnsigned over them), else
     // minUnsigned over everything considered; fragment.max (:803-830) with positives.  "present" is
@@ -1571,9 +1460,7 @@ static int32_t bsi_minmax(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* 
                           uint32_t bit_depth, uint32_t mode, const fbk_batch* filter, const uint32_t* rows_f,
                           int64_t* out_vals, uint64_t* out_counts) {
   FBK_ENTER(ctx);
-  if (!ctx || !batch || (n_shards && (!base_rows || !out_vals || !out_counts)) || (filter && n_shards && !rows_f))
-    return fail(FBK_E_INVALID, "NULL argument");
-  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (int32_t rc = bsi_aggregate_args_ok(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f, out_vals, out_counts)) return rc;
   if (n_shards == 0) return FBK_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
@@ -1606,27 +1493,19 @@ int32_t fbk_bsi_add(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* rows_x, ui
   if (n_groups * (D + 1) > (1ull << 27)) return fail(FBK_E_INVALID, "too many groups in one call");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  fbk_batch* o = nullptr;
-  if (int32_t rc = alloc_cell_batch(ctx, n_groups * (D + 1), &o)) return rc;
-  DevBuf drx, dry, druns;
-  int32_t rc = upload_rows(ctx, rows_x, n_groups * depth_x, x->n_rows, drx);
-  if (!rc) rc = upload_rows(ctx, rows_y, n_groups * depth_y, y->n_rows, dry);
-  if (!rc) {
-    hipError_t e = druns.alloc(ctx, std::max<uint64_t>(n_groups * (D + 1) * fbk::kSlots, 1) * 4);
-    if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("bsi_add: ") + hipGetErrorString(e));
-  }
-  if (!rc && n_groups) {
+  DevBuf drx, dry;
+  CellOutput out;
+  if (int32_t rc = out.alloc(ctx, n_groups * (D + 1), 0, "bsi_add")) return rc;
+  if (int32_t rc = upload_rows(ctx, rows_x, n_groups * depth_x, x->n_rows, drx)) return rc;
+  if (int32_t rc = upload_rows(ctx, rows_y, n_groups * depth_y, y->n_rows, dry)) return rc;
+  if (n_groups) {
     hipLaunchKernelGGL(fbk::k_bsi_add, dim3(uint32_t(n_groups * fbk::kSlots)), dim3(256), 0, ctx->stream, x->d_slots, x->d_arena,
-                       drx.as<uint32_t>(), depth_x, y->d_slots, y->d_arena, dry.as<uint32_t>(), depth_y, n_groups, o->d_arena,
-                       o->d_slots, druns.as<uint32_t>());
-    rc = finish_output(ctx, o, flags, druns.as<uint32_t>(), nullptr, 0, nullptr);
+                       drx.as<uint32_t>(), depth_x, y->d_slots, y->d_arena, dry.as<uint32_t>(), depth_y, n_groups, out.batch()->d_arena,
+                       out.batch()->d_slots, out.runs());
+    if (int32_t rc = out.finish(flags, 0, nullptr)) return rc;
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (rc) {
-    free_batch_storage(o);
-    return rc;
-  }
-  *out_batch = o;
+  *out_batch = out.release();
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 
@@ -1646,49 +1525,31 @@ int32_t fbk_shift(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* rows, co
   if (int32_t rc = set_device(ctx)) return rc;
   fbk_batch* bb = const_cast<fbk_batch*>(batch);
   if (int32_t rc = refresh_slots(bb)) return rc;
-  fbk_batch* o = nullptr;
-  if (int32_t rc = alloc_cell_batch(ctx, n_rows, &o)) return rc;
+  DevBuf drows, dcarry;
+  CellOutput out;
+  if (int32_t rc = out.alloc(ctx, n_rows, n_rows, "shift")) return rc;
+  fbk_batch* o = out.batch();
   // output keys: the keys of the shifted row (of the carry row's successor shard for a row that
   // exists only because a bit was carried into it)
   for (uint64_t i = 0; i < n_rows; ++i) {
     uint64_t high = 0;
-    bool found = false;
-    const uint32_t cand[2] = {rows[i], carry_rows ? carry_rows[i] : FBK_NO_ROW};
-    for (int c = 0; c < 2 && !found; ++c) {
-      if (cand[c] == FBK_NO_ROW) continue;
-      for (int sl = 0; sl < fbk::kSlots; ++sl) {
-        const uint64_t is = uint64_t(cand[c]) * fbk::kSlots + sl;
-        if (fbk::slot_type(batch->h_slots[is]) != fbk::kTypeNil) {
-          high = (batch->h_keys[is] & ~15ull) + (c == 1 ? 16 : 0);
-          found = true;
-          break;
-        }
-      }
+    if (rows[i] == FBK_NO_ROW || !row_key_high(batch, rows[i], &high)) {
+      if (carry_rows && carry_rows[i] != FBK_NO_ROW && row_key_high(batch, carry_rows[i], &high)) high += 16;
     }
-    for (int sl = 0; sl < fbk::kSlots; ++sl) o->h_keys[i * fbk::kSlots + sl] = high | uint64_t(sl);
+    set_row_keys(o, i, high);
   }
-  DevBuf drows, dcarry, druns, dcnt;
-  int32_t rc = upload_rows(ctx, rows, n_rows, UINT32_MAX, drows);  // validated above (FBK_NO_ROW is legal here)
-  if (!rc && carry_rows) rc = upload_rows(ctx, carry_rows, n_rows, UINT32_MAX, dcarry);
-  if (!rc) {
-    hipError_t e = druns.alloc(ctx, std::max<uint64_t>(n_rows * fbk::kSlots, 1) * 4);
-    if (e == hipSuccess) e = dcnt.alloc(ctx, std::max<uint64_t>(n_rows, 1) * 8);
-    if (e == hipSuccess && n_rows) e = hipMemsetAsync(dcnt.p, 0, n_rows * 8, ctx->stream);
-    if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("shift: ") + hipGetErrorString(e));
-  }
+  if (int32_t rc = upload_rows(ctx, rows, n_rows, UINT32_MAX, drows)) return rc;  // validated above (FBK_NO_ROW is legal here)
+  if (carry_rows)
+    if (int32_t rc = upload_rows(ctx, carry_rows, n_rows, UINT32_MAX, dcarry)) return rc;
   const bool enc = (flags & FBK_SETOP_OPTIMIZE) && ctx->opt.setop_direct_encode == 2;  // optimize() inside the kernel
-  if (!rc && n_rows) {
+  if (n_rows) {
     hipLaunchKernelGGL(fbk::k_shift, dim3(uint32_t((n_rows * fbk::kSlots + 3) / 4)), dim3(256), 0, ctx->stream, batch->d_slots,
                        batch->d_arena, drows.as<uint32_t>(), carry_rows ? dcarry.as<uint32_t>() : (const uint32_t*)nullptr, n_rows,
-                       o->d_arena, o->d_slots, druns.as<uint32_t>(), dcnt.as<u64>(), uint32_t(enc));
-    rc = finish_output(ctx, o, enc ? (flags & ~uint32_t(FBK_SETOP_OPTIMIZE)) : flags, druns.as<uint32_t>(), dcnt.as<u64>(), n_rows, out_counts, enc != 0);
+                       o->d_arena, o->d_slots, out.runs(), out.counts(), uint32_t(enc));
+    if (int32_t rc = out.finish(enc ? (flags & ~uint32_t(FBK_SETOP_OPTIMIZE)) : flags, n_rows, out_counts, enc)) return rc;
   }
   (void)hipStreamSynchronize(ctx->stream);
-  if (rc) {
-    free_batch_storage(o);
-    return rc;
-  }
-  *out_batch = o;
+  *out_batch = out.release();
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 
@@ -1802,15 +1663,7 @@ int32_t fbk_bsi_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base
   if (flags & ~FBK_SETOP_OPTIMIZE) return fail(FBK_E_INVALID, "unknown flags");
   *out_batch = nullptr;
   BsiProg prog;
-  switch (op) {  // rangeOp, fragment.go:937-950
-    case FBK_BSI_EQ: gen_eq(prog, bit_depth, predicate); break;
-    case FBK_BSI_NEQ: gen_neq(prog, bit_depth, predicate); break;
-    case FBK_BSI_LT: gen_lt(prog, bit_depth, predicate, false); break;
-    case FBK_BSI_LTE: gen_lt(prog, bit_depth, predicate, true); break;
-    case FBK_BSI_GT: gen_gt(prog, bit_depth, predicate, false); break;
-    case FBK_BSI_GTE: gen_gt(prog, bit_depth, predicate, true); break;
-    default: return fail(FBK_E_INVALID, "invalid range operation");  // ErrInvalidRangeOperation
-  }
+  if (!gen_range_op(prog, op, bit_depth, predicate)) return fail(FBK_E_INVALID, "invalid range operation");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
   return run_bsi_program(ctx, batch, base_rows, n_shards, bit_depth, prog, flags, out_batch, out_counts);
@@ -1820,45 +1673,27 @@ int32_t fbk_bsi_range_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* 
                           uint32_t bit_depth, int64_t predicate, const fbk_batch* filter, const uint32_t* rows_f, int64_t* out_sums,
                           uint64_t* out_counts) try {
   FBK_ENTER(ctx);
-  if (!ctx || !batch || (n_shards && (!base_rows || !out_sums || !out_counts)) || (filter && n_shards && !rows_f))
-    return fail(FBK_E_INVALID, "NULL argument");
-  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (int32_t rc = bsi_aggregate_args_ok(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f, out_sums, out_counts)) return rc;
   if (op < FBK_BSI_EQ || op > FBK_BSI_GTE) return fail(FBK_E_INVALID, "invalid range operation");
   if (n_shards == 0) return FBK_OK;
   fbk::RangeSumPlan pl;
   if (!plan_range_sum(op, bit_depth, predicate, pl)) {
-    // the reference's own two steps: the range as a Row, then fragment.sum with that Row (∩ the caller's filter) as the filter
     fbk_batch* rng = nullptr;
     if (int32_t rc = fbk_bsi_range(ctx, batch, base_rows, n_shards, op, bit_depth, predicate, 0, &rng, nullptr)) return rc;
-    std::vector<uint32_t> ident(n_shards);
-    for (uint32_t s = 0; s < n_shards; ++s) ident[s] = s;
-    int32_t rc = FBK_OK;
-    if (filter) {
-      fbk_batch* both = nullptr;
-      rc = fbk_setop(ctx, FBK_OP_AND, rng, ident.data(), filter, rows_f, n_shards, 0, &both, nullptr);
-      (void)fbk_batch_free(ctx, rng);
-      rng = both;
-    }
-    if (!rc) rc = fbk_bsi_sum(ctx, batch, base_rows, n_shards, bit_depth, rng, ident.data(), out_sums, out_counts);
-    if (rng) (void)fbk_batch_free(ctx, rng);
-    return rc;
+    return bsi_sum_over_range(ctx, batch, base_rows, n_shards, bit_depth, rng, filter, rows_f, out_sums, out_counts);
   }
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
-  DevBuf dbase, drf, d4, dplan;
-  if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
-  if (filter)
-    if (int32_t rc = upload_rows(ctx, rows_f, n_shards, filter->n_rows, drf)) return rc;
+  BsiShardOperands ops;
+  if (int32_t rc = ops.upload(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f)) return rc;
+  DevBuf d4, dplan;
   HIP_TRY(d4.alloc(ctx, uint64_t(n_shards) * 32));
   HIP_TRY(dplan.alloc(ctx, sizeof(pl)));
   HIP_TRY(hipMemcpyAsync(dplan.p, &pl, sizeof(pl), hipMemcpyHostToDevice, ctx->stream));
-  if (int32_t rc = bsi_range_sum_launch(ctx, batch, dbase.as<uint32_t>(), n_shards, pl, dplan.as<fbk::RangeSumPlan>(), filter, drf.as<uint32_t>(), d4.as<u64>()))
+  if (int32_t rc = bsi_range_sum_launch(ctx, batch, ops.base(), n_shards, pl, dplan.as<fbk::RangeSumPlan>(), filter, ops.filter_rows(), d4.as<u64>()))
     return rc;
-  std::vector<u64> h4(uint64_t(n_shards) * 4);
-  D2H back(ctx);
-  HIP_TRY(back.add(h4.data(), d4.p, h4.size() * 8));
-  HIP_TRY(back.finish());
+  std::vector<u64> h4;
+  if (int32_t rc = download_words(ctx, d4, uint64_t(n_shards) * 4, h4)) return rc;
   for (uint32_t s = 0; s < n_shards; ++s) {
     // the scanned class's magnitudes and the other class's: which of them is positive decides the signs (Total():
     // int64(psum) - int64(nsum), roaring/filter.go:1106-1108)
@@ -1900,53 +1735,36 @@ int32_t fbk_bsi_between_sum_plan(uint32_t bit_depth, int64_t lo, int64_t hi, uin
 int32_t fbk_bsi_range_between_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards, uint32_t bit_depth,
                                   int64_t lo, int64_t hi, const fbk_batch* filter, const uint32_t* rows_f, int64_t* out_sums, uint64_t* out_counts) try {
   FBK_ENTER(ctx);
-  if (!ctx || !batch || (n_shards && (!base_rows || !out_sums || !out_counts)) || (filter && n_shards && !rows_f))
-    return fail(FBK_E_INVALID, "NULL argument");
-  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (int32_t rc = bsi_aggregate_args_ok(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f, out_sums, out_counts)) return rc;
   if (n_shards == 0) return FBK_OK;
   fbk::BetweenSumPlan pl;
   // the one-pass kernel keeps four fragments per wavefront: dense batches only (half a container per wavefront)
   if (!batch->dense || !plan_between_sum(bit_depth, lo, hi, pl)) {
     fbk_batch* rng = nullptr;
     if (int32_t rc = fbk_bsi_range_between(ctx, batch, base_rows, n_shards, bit_depth, lo, hi, 0, &rng, nullptr)) return rc;
-    std::vector<uint32_t> ident(n_shards);
-    for (uint32_t s = 0; s < n_shards; ++s) ident[s] = s;
-    int32_t rc = FBK_OK;
-    if (filter) {
-      fbk_batch* both = nullptr;
-      rc = fbk_setop(ctx, FBK_OP_AND, rng, ident.data(), filter, rows_f, n_shards, 0, &both, nullptr);
-      (void)fbk_batch_free(ctx, rng);
-      rng = both;
-    }
-    if (!rc) rc = fbk_bsi_sum(ctx, batch, base_rows, n_shards, bit_depth, rng, ident.data(), out_sums, out_counts);
-    if (rng) (void)fbk_batch_free(ctx, rng);
-    return rc;
+    return bsi_sum_over_range(ctx, batch, base_rows, n_shards, bit_depth, rng, filter, rows_f, out_sums, out_counts);
   }
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows)) return rc;
-  DevBuf dbase, drf, d4, dplan;
-  if (int32_t rc = upload_rows(ctx, base_rows, n_shards, batch->n_rows, dbase)) return rc;
-  if (filter)
-    if (int32_t rc = upload_rows(ctx, rows_f, n_shards, filter->n_rows, drf)) return rc;
+  BsiShardOperands ops;
+  if (int32_t rc = ops.upload(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f)) return rc;
+  DevBuf d4, dplan;
   HIP_TRY(d4.alloc(ctx, uint64_t(n_shards) * 32));
   HIP_TRY(hipMemsetAsync(d4.p, 0, uint64_t(n_shards) * 32, ctx->stream));
   HIP_TRY(dplan.alloc(ctx, sizeof(pl)));
   HIP_TRY(hipMemcpyAsync(dplan.p, &pl, sizeof(pl), hipMemcpyHostToDevice, ctx->stream));
+  const FilterArgs f(filter, ops.filter_rows());
   {
     KernelSpan span(ctx);
     // half a container per wavefront, bsi_planes_ahead planes in flight (the quarter-container form of round 3 was removed
     // again: slower once the planes in flight were counted by hand, and two of its instantiations failed the in-flight check)
     auto kern = fbk::k_bsi_between_sum_part<8, 3>;
-    hipLaunchKernelGGL(kern, dim3(uint32_t(uint64_t(n_shards) * fbk::kSlots * 2)), dim3(64), 0, ctx->stream, batch->d_arena, dbase.as<uint32_t>(), n_shards,
-                       dplan.as<fbk::BetweenSumPlan>(), filter ? filter->d_slots : (const Slot*)nullptr, filter ? filter->d_arena : (const uint8_t*)nullptr,
-                       drf.as<uint32_t>(), d4.as<u64>());
+    hipLaunchKernelGGL(kern, dim3(uint32_t(uint64_t(n_shards) * fbk::kSlots * 2)), dim3(64), 0, ctx->stream, batch->d_arena, ops.base(), n_shards,
+                       dplan.as<fbk::BetweenSumPlan>(), f.slots, f.arena, f.rows, d4.as<u64>());
   }
   HIP_TRY(hipGetLastError());
-  std::vector<u64> h4(uint64_t(n_shards) * 4);
-  D2H back(ctx);
-  HIP_TRY(back.add(h4.data(), d4.p, h4.size() * 8));
-  HIP_TRY(back.finish());
+  std::vector<u64> h4;
+  if (int32_t rc = download_words(ctx, d4, uint64_t(n_shards) * 4, h4)) return rc;
   for (uint32_t s = 0; s < n_shards; ++s) {
     const uint64_t s0 = h4[s * 4 + 0], s1 = h4[s * 4 + 1];
     out_sums[s] = int64_t((pl.class_pos[0] ? s0 : 0ull - s0) + (pl.class_pos[1] ? s1 : 0ull - s1));

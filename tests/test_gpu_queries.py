@@ -1673,3 +1673,85 @@ def test_pair_count_arrays_on_every_row_and_half_boundary(gpu_ctx, oracle):
         gpu_ctx.set_option("pair_kernels", 0)
     A.free()
     Bt.free()
+
+
+def _key_rule_rows():
+    """Four rows whose first non-nil container sits in slot 5, 0, nowhere and 15: an array, a bitmap and a run among them."""
+    from featurebase_amd.roaring import Container
+
+    bm = np.zeros(1024, dtype=np.uint64)
+    bm[::2] = 0x00FF00FF00FF00FF
+    return [
+        {(7 << 4) | 5: Container.array([1, 2, 700, 40000]), (7 << 4) | 9: Container.bitmap(bm, 16384)},
+        {3 << 4: Container.run([(10, 20), (300, 4000)])},
+        {},
+        {(9 << 4) | 15: Container.array([5, 6, 65535])},  # (its last column is what a shift carries into the next shard)
+    ]
+
+
+@pytest.mark.parametrize("flags", [0, L.SETOP_OPTIMIZE])
+def test_output_keys_follow_the_first_container(gpu_ctx, flags):
+    """The key of an output row of fold / Flip / Shift is (high | slot), high = the high key bits of the first non-nil container
+    of its source row: the group's first row for a fold (none: 0), the flipped row (none: row ordinal << 4), the shifted row,
+    else the carry row's + 16, else 0.  Every key a download reports is checked; the fifth shift entry is there because the
+    carried key of the second one belongs to an empty row, which a download does not report."""
+    NO = gpu_ctx.NO_ROW
+    batch = gpu_ctx.upload(_key_rule_rows())
+
+    def highs(out, want):
+        rows = out.download()
+        assert len(rows) == len(want)
+        for i, (row, high) in enumerate(zip(rows, want)):
+            for key in row:
+                assert key & ~15 == high, (i, hex(key), hex(high))
+        return rows
+
+    out, _ = gpu_ctx.fold_n(L.OP_OR, batch, [[0, 2], [2, 0], [2, 2]], flags)
+    rows = highs(out, [7 << 4, 0, 0])
+    assert [sorted(k & 15 for k in r) for r in rows] == [[5, 9], [5, 9], []]
+    out.free()
+
+    out, _ = gpu_ctx.flip(batch, [0, 1, 2, 3], 0, (1 << 20) - 1, flags)
+    rows = highs(out, [7 << 4, 3 << 4, 2 << 4, 9 << 4])
+    assert all(sorted(k & 15 for k in r) == list(range(16)) for r in rows)  # (no container here is full: none flips to nil)
+    out.free()
+
+    out, _ = gpu_ctx.shift(batch, [0, NO, 2, 3, NO], [NO, 0, 2, NO, 3], flags)
+    rows = highs(out, [7 << 4, (7 << 4) + 16, 0, 9 << 4, (9 << 4) + 16])
+    assert [sorted(k & 15 for k in r) for r in rows] == [[5, 9], [], [], [15], [0]]
+    assert set(rows[4]) == {10 << 4}
+    out.free()
+    batch.free()
+
+
+@pytest.mark.parametrize("flags", [0, L.SETOP_OPTIMIZE])
+def test_materialising_calls_on_empty_input(gpu_ctx, flags):
+    """Zero rows, groups or shards — and TopK counts that are all zero — still give FBK_OK and a batch: of no rows (one for
+    Distinct rows, its trailing empty row), which downloads to no containers and frees cleanly."""
+    import ctypes as C
+
+    batch = gpu_ctx.upload(_key_rule_rows())
+
+    def check_empty(out, n_rows):
+        assert out.h.value
+        assert out.info() == (n_rows, 0, 0)
+        assert out.download() == [{}] * n_rows
+        out.free()
+
+    check_empty(gpu_ctx.flip(batch, [], 0, 10, flags)[0], 0)
+    check_empty(gpu_ctx.shift(batch, [], None, flags)[0], 0)
+    check_empty(gpu_ctx.shift(batch, [], [], flags)[0], 0)
+    h = C.c_void_p()  # (the wrapper reshapes its row lists: zero groups go through the C ABI directly)
+    L.check(gpu_ctx.lib.fbk_bsi_add(gpu_ctx.h, batch.h, None, 3, batch.h, None, 2, 0, flags, C.byref(h)))
+    from featurebase_amd.roaring import Batch
+
+    check_empty(Batch(gpu_ctx, h.value), 0)
+    check_empty(gpu_ctx.bsi_range(batch, [], L.BSI_LT, 2, 1, flags)[0], 0)
+    check_empty(gpu_ctx.bsi_range_between(batch, [], 2, -1, 2, flags)[0], 0)
+    out, depth = gpu_ctx.topk_bsi(batch, [[2, 2]], flags=flags)  # (row 2 has no containers: every count is 0)
+    assert depth == 0
+    check_empty(out, 0)
+    out, pos, neg, counts = gpu_ctx.bsi_distinct_rows(batch, [], 2, flags=flags)
+    assert pos.size == 0 and neg.size == 0 and counts.size == 0
+    check_empty(out, 1)
+    batch.free()
