@@ -53,6 +53,7 @@ namespace {
 // not reliable there.
 thread_local std::string g_err = "";
 thread_local fbk_ctx* g_scope_ctx = nullptr;  // context of the API call running on this thread
+thread_local bool g_scope_quiet = false;      // ... and whether that call is a quiet one (FBK_ENTER_QUIET)
 thread_local fbk_group* g_scope_group = nullptr;  // group of the fbk_group_* call running on this thread
 void ctx_record_error(fbk_ctx* ctx, int32_t code, const std::string& msg);  // defined after fbk_ctx
 void group_record_error(fbk_group* g, int32_t code, const std::string& msg);  // fbk_group_api.inc
@@ -65,13 +66,30 @@ int32_t fail(int32_t code, const std::string& msg) {
   return code;
 }
 
-// first statement of every entry point that takes a context
+// first statement of every entry point that takes a context.  FBK_ENTER also ends the residency of the context's hot plan
+// (ctx_loud_enter, after fbk_ctx): whatever the call enqueues may push the plan's rows out of the Infinity Cache.
+// FBK_ENTER_QUIET keeps it: ONLY for entry points that move at most a few words of device memory — the three
+// fbk_plan_intersection_count* calls, fbk_plan_total, fbk_plan_read, fbk_comm_all_reduce_u64, fbk_comm_fence,
+// fbk_get_option, fbk_set_option, fbk_synchronize and the last-error getters.  Anything new takes FBK_ENTER.
+void ctx_loud_enter(fbk_ctx* ctx);
+void ctx_loud_leave(fbk_ctx* ctx);
 struct ApiScope {
   fbk_ctx* prev;
-  explicit ApiScope(fbk_ctx* c) : prev(g_scope_ctx) { g_scope_ctx = c; }
-  ~ApiScope() { g_scope_ctx = prev; }
+  fbk_ctx* loud;
+  bool prev_quiet;
+  explicit ApiScope(fbk_ctx* c, bool quiet = false) : prev(g_scope_ctx), loud(quiet ? nullptr : c), prev_quiet(g_scope_quiet) {
+    g_scope_ctx = c;
+    g_scope_quiet = quiet;
+    if (loud) ctx_loud_enter(loud);
+  }
+  ~ApiScope() {
+    if (loud) ctx_loud_leave(loud);
+    g_scope_ctx = prev;
+    g_scope_quiet = prev_quiet;
+  }
 };
 #define FBK_ENTER(ctx) ApiScope api_scope_(ctx)
+#define FBK_ENTER_QUIET(ctx) ApiScope api_scope_(ctx, true)
 
 #define HIP_TRY(expr)                                                                          \
   do {                                                                                         \
@@ -199,6 +217,11 @@ struct fbk_ctx {
   std::vector<struct fbk_cache_entry*> cache_zombies;  // invalidated while pinned
   uint64_t cache_bytes = 0, cache_cap_bytes = 128ull << 30, cache_clock = 0;
   uint64_t cache_hits = 0, cache_misses = 0, cache_evictions = 0;
+  // The plan whose dense count was the last device work of any size this context enqueued (plan_icount_enqueue_locked): its
+  // next count finds the rows in the Infinity Cache and takes k_icount_dense_resident.  Written under `mu`, cleared without
+  // it by every entry point that is not quiet (FBK_ENTER); while such a call is in flight no plan becomes hot.
+  std::atomic<const fbk_plan*> hot_plan{nullptr};
+  std::atomic<int> loud_calls{0};
 };
 
 // Host mirror of one device-resident batch.
@@ -233,6 +256,13 @@ struct fbk_batch {
   // known: uploads check their descriptors, kernel outputs are 8 KiB cells.  Batches that are not go to k_icount2.
   bool ring_regular = false;
 };
+namespace {
+void ctx_loud_enter(fbk_ctx* ctx) {
+  ctx->loud_calls.fetch_add(1);
+  ctx->hot_plan.store(nullptr);
+}
+void ctx_loud_leave(fbk_ctx* ctx) { ctx->loud_calls.fetch_sub(1); }
+}  // namespace
 inline bool ring_fits(uint32_t type, uint32_t len) { return !((type == fbk::kTypeArray && len > 4096u) || (type == fbk::kTypeRun && len > 2048u)); }
 
 namespace {
@@ -401,6 +431,7 @@ struct DevBuf {
 
 int32_t set_device(fbk_ctx* ctx) {
   g_scope_ctx = ctx;  // entry points that take the context from a batch / plan handle (ApiScope restores the caller's)
+  if (!g_scope_quiet) ctx->hot_plan.store(nullptr);  // (... entered with a NULL context: FBK_ENTER could not end the hot plan's residency)
   HIP_TRY(hipSetDevice(ctx->device));
   ctx->h_stage_used = 0;
   return FBK_OK;
@@ -689,7 +720,7 @@ const char* fbk_last_error(fbk_ctx* ctx) {
 }
 
 int32_t fbk_last_error_r(fbk_ctx* ctx, char* buf, uint64_t cap, int32_t* out_code) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   std::string msg;
   int32_t code = 0;
   if (ctx) {
@@ -866,19 +897,20 @@ int32_t fbk_close(fbk_ctx* ctx) try {
   }
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   if (ctx->root) ctx->root->children.fetch_sub(1);
+  api_scope_.loud = nullptr;  // (nothing of the context is touched when the scope ends)
   delete ctx;
   return FBK_OK;
 } FBK_ABI_CATCH(nullptr)  // (the context may be gone: nothing is recorded on it)
 
 int32_t fbk_set_option(fbk_ctx* ctx, const char* name, int64_t value) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx || !name) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   return option_set(ctx->opt, name, value);
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_get_option(fbk_ctx* ctx, const char* name, int64_t* out_value) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx || !name || !out_value) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (ctx->kt_armed && std::strcmp(name, "last_kernel_ns") == 0) {
@@ -909,7 +941,7 @@ int32_t fbk_set_stream(fbk_ctx* ctx, void* hip_stream) try {
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_synchronize(fbk_ctx* ctx) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx) return fail(FBK_E_INVALID, "ctx is NULL");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
@@ -1403,6 +1435,7 @@ struct fbk_plan {
   uint32_t* d_wave_counts = nullptr;
   uint32_t* d_ring_ctl = nullptr;  // k_icount3: word 0 is OR-ed with 1 by a block that gave up on a wait (never in a correct run; fbk_plan_read reports it)
   uint64_t items_va = ~0ull, items_vb = ~0ull;
+  bool last_rev = false;  // direction of the plan's last dense count (k_icount_dense_resident's `rev`; the cold kernel counts as forward)
 };
 
 namespace {
@@ -1522,6 +1555,8 @@ void free_plan_storage(fbk_plan* p) {
   if (p->d_wave_counts) (void)ctx_free(p->ctx, p->d_wave_counts);
   if (p->d_ring_ctl) (void)ctx_free(p->ctx, p->d_ring_ctl);
   free_batch_storage(p->out);
+  const fbk_plan* self = p;
+  if (p->ctx) p->ctx->hot_plan.compare_exchange_strong(self, nullptr);  // (a later plan may get this address)
   delete p;
 }
 
@@ -1576,6 +1611,24 @@ int32_t plan_icount_enqueue_locked(fbk_ctx* ctx, fbk_plan* p, u64* fused_total =
     // all-bitmap rows: pure streaming kernel.  slots-per-block 16 = one block per row
     // pair, plain store; smaller groups = more blocks + one atomicAdd per block.
     const int spb = int(ctx->opt.dense_spb);
+    // A plan whose rows the Infinity Cache can hold, counted again with nothing else enqueued on the context in between
+    // (hot_plan): the rows are where the last launch left them, and k_icount_dense_resident reads them in the reverse
+    // of that launch's order — what was read last, and is surest to be resident still, first.  Everything else, the
+    // plan's first count included, is cold data to this context: the non-temporal kernel below, unchanged.
+    // (Not seen from here: other contexts, forks and processes on the device.  A hot launch after they evicted the rows
+    // reads HBM with plain loads — DESIGN.md §9 has the cost.)
+    const bool hot = spb == 16 && ctx->hot_plan.load() == p &&
+                     fbk::dense_footprint_bound(p->n_pairs, p->a->n_rows, p->b->n_rows, p->a == p->b) <= fbk::kDenseResidentMaxBytes;
+    if (hot) {
+      // one block per compute unit: at 256 MiB 35.0 us against 38.1-39.5 with two to four (and 41.5 for the non-temporal kernel) —
+      // the fewer blocks walk the rows at a time, the closer a launch is to the mirror of the one before (profiles/dense_resident.txt)
+      const uint32_t grid = std::min<uint32_t>(np, uint32_t(ctx->n_cu > 0 ? ctx->n_cu : 256));
+      p->last_rev = !p->last_rev;
+      hipLaunchKernelGGL(fbk::k_icount_dense_resident<false>, dim3(grid), dim3(256), 0, ctx->stream, p->a->d_arena, p->d_rows_a, p->b->d_arena,
+                         p->d_rows_b, p->d_counts, fused_total, p->d_done, np, accum, p->last_rev ? 1u : 0u);
+      HIP_TRY(hipGetLastError());
+      return FBK_OK;  // (still the context's hot plan)
+    }
     if (spb != 16) HIP_TRY(hipMemsetAsync(p->d_counts, 0, p->n_pairs * sizeof(u64), ctx->stream));
 #define FBK_LAUNCH_DENSE(S)                                                                                       \
   hipLaunchKernelGGL(fbk::k_icount_dense<S>, dim3(np*(16 / S)), dim3(256), 0, ctx->stream, p->a->d_arena,         \
@@ -1588,7 +1641,15 @@ int32_t plan_icount_enqueue_locked(fbk_ctx* ctx, fbk_plan* p, u64* fused_total =
       default: FBK_LAUNCH_DENSE(16); break;
     }
 #undef FBK_LAUNCH_DENSE
+    HIP_TRY(hipGetLastError());
+    // the plan is hot from here on, unless a call that is not quiet is running on the context right now (another thread's:
+    // whatever it enqueues may come after this launch)
+    p->last_rev = false;
+    ctx->hot_plan.store(p);
+    if (ctx->loud_calls.load() != 0) ctx->hot_plan.store(nullptr);
+    return FBK_OK;
   } else {
+    ctx->hot_plan.store(nullptr);  // (the count entry points are quiet: a count over encoded rows ends a dense plan's residency here)
     const bool pk2 = use_pair_kernels2(ctx, p->a, p->b, -1);
 #ifdef FBK_EXPERIMENTS
     const bool pk3 = ctx->opt.pair_kernels == 3 && p->a->ring_regular && p->b->ring_regular;
@@ -1766,7 +1827,7 @@ int32_t fbk_plan_free(fbk_ctx* ctx, fbk_plan* plan) try {
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_plan_intersection_count(fbk_ctx* ctx, fbk_plan* plan) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
@@ -1774,7 +1835,7 @@ int32_t fbk_plan_intersection_count(fbk_ctx* ctx, fbk_plan* plan) try {
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_plan_intersection_count_total(fbk_ctx* ctx, fbk_plan* plan, void* device_total_or_null) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
@@ -1783,7 +1844,7 @@ int32_t fbk_plan_intersection_count_total(fbk_ctx* ctx, fbk_plan* plan, void* de
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_plan_intersection_count_accumulate(fbk_ctx* ctx, fbk_plan* plan, void* device_accum) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx || !plan || !device_accum) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
@@ -1804,7 +1865,7 @@ int32_t fbk_plan_setop(fbk_ctx* ctx, fbk_plan* plan, int32_t op, uint32_t flags)
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_plan_total(fbk_ctx* ctx, fbk_plan* plan, void* device_total_or_null) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
@@ -1815,7 +1876,7 @@ int32_t fbk_plan_total(fbk_ctx* ctx, fbk_plan* plan, void* device_total_or_null)
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_plan_read(fbk_ctx* ctx, fbk_plan* plan, uint64_t* out_counts, uint64_t* out_total) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;

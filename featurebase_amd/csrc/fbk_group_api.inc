@@ -412,7 +412,7 @@ int32_t fbk_group_plan_intersection_count_total(fbk_group* g, fbk_plan* const* p
   int32_t rc = FBK_OK;
   for (uint32_t m = 0; m < n && !rc; ++m) {
     fbk_ctx* c = g->members[m];
-    FBK_ENTER(c);
+    FBK_ENTER_QUIET(c);  // (the member's hot plan stays hot, as in fbk_plan_intersection_count_total)
     rc = set_device(c);
     if (rc) break;
     if (plans[m]) {
@@ -684,7 +684,7 @@ int32_t fbk_comm_init(fbk_ctx* ctx, const uint8_t* id, int32_t n_ranks, int32_t 
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_comm_all_reduce_u64(fbk_ctx* ctx, void* device_words, uint64_t n_words) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx || !device_words) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (!ctx->comm) return fail(FBK_E_INVALID, "comm: the context has no communicator (fbk_comm_init)");
@@ -699,7 +699,7 @@ int32_t fbk_comm_all_reduce_u64(fbk_ctx* ctx, void* device_words, uint64_t n_wor
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_comm_fence(fbk_ctx* ctx) try {
-  FBK_ENTER(ctx);
+  FBK_ENTER_QUIET(ctx);
   if (!ctx) return fail(FBK_E_INVALID, "NULL argument");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (!ctx->comm) return fail(FBK_E_INVALID, "comm: the context has no communicator (fbk_comm_init)");

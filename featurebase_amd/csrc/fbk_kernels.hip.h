@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fbk_dense_policy.h"
+
 namespace fbk {
 
 constexpr int kWave = 64;
@@ -96,7 +98,9 @@ __device__ __forceinline__ uint32_t wave_reduce_add(uint32_t v) {
 // per kernel and never reused by the same launch, so they should not displace each other
 // in L2 / Infinity Cache: measured on MI355X with a 1 GiB working set, the dense
 // |A∩B| kernel goes from 5.69 TB/s (plain loads) to 6.54 TB/s with `nt` loads
-// (profiles/tune_dense_r01.txt).
+// (profiles/tune_dense_r01.txt).  The price: the hint also keeps most of the lines out of the Infinity Cache, so rows that
+// ARE read again by the next launch come from HBM again — a plan that fits the cache and is counted repeatedly takes
+// k_icount_dense_resident (plain loads) instead.
 __device__ __forceinline__ ulonglong2 ld_stream(const ulonglong2* p) {
   ulonglong2 v;
   v.x = __builtin_nontemporal_load(&p->x);
@@ -564,6 +568,52 @@ __global__ void __launch_bounds__(256) k_count_range(const Slot* __restrict__ sl
   if (lane == 0) out[r] = (u64)total;
 }
 
+// Block tail of the dense count kernels (k_icount_dense, k_icount_dense_resident).  dense_publish: thread 0 writes one pair's
+// count — kWhole: the block counted the whole pair (plain store; for the `total` form an agent-scope atomic store, see below),
+// else one of several blocks of the pair adds its share.
+template <bool kWhole>
+__device__ __forceinline__ void dense_publish(u64* cell, u64 tot, bool ticketed) {
+  if (!kWhole) atomicAdd(cell, tot);
+  else if (ticketed) __hip_atomic_store(cell, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  else *cell = tot;
+}
+// dense_block_tail: every thread of the block, after thread 0 has published the block's pairs; `blk` (thread 0's) is the sum of
+// what the block counted.
+__device__ __forceinline__ void dense_block_tail(u64 blk, u64* __restrict__ out, u64* __restrict__ total, uint32_t* __restrict__ done,
+                                                 uint32_t n_pairs, u64* __restrict__ accum) {
+  __shared__ uint32_t s_last;
+  if (threadIdx.x == 0) {
+    s_last = 0;
+    if (!total) {
+      // per-node reduce by accumulation: every block adds its count to *accum, which the caller
+      // zeroed beforehand — no ticket, no final pass, nothing serial behind the last workgroup
+      if (accum && blk) atomicAdd(accum, blk);
+    } else {
+      // Fused per-node reduce (executeCount's reduceFn, executor.go:5880): the block that
+      // finishes last sums the per-pair counts, so one step of the hot path is ONE launch.
+      // The blocks run on 8 XCDs with separate L2s: the count is published with an agent-scope
+      // atomic store (write-through, no L2-wide flush: a release FENCE here costs a full L2
+      // write-back per block and doubled the kernel time), completed before the ticket is taken.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      s_last = (atomicAdd(done, 1u) == gridDim.x - 1) ? 1u : 0u;
+    }
+  }
+  if (!total) return;
+  __syncthreads();
+  if (!s_last) return;
+  u64 acc = 0;  // agent-scope loads: straight from the coherence point, no stale L2 lines
+  for (uint32_t i = threadIdx.x; i < n_pairs; i += 256) acc += __hip_atomic_load(&out[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
+  __shared__ u64 tpart[4];
+  if ((threadIdx.x & 63) == 0) tpart[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    *total = tpart[0] + tpart[1] + tpart[2] + tpart[3];
+    *done = 0;  // ready for the next launch (stream ordered)
+  }
+}
+
 // |A ∩ B| for dense rows: every slot a bitmap container and each row one contiguous
 // 128 KiB block (config 2, the HBM-roofline case).  One 256-thread block per
 // (pair, group of SPB slots); thread t streams 16-byte chunks t, t+256, ... of its
@@ -603,7 +653,6 @@ __global__ void __launch_bounds__(256) k_icount_dense(const uint8_t* __restrict_
   }
   c = wave_reduce_add(c);
   __shared__ uint32_t part[4];
-  __shared__ uint32_t s_last;
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
   __syncthreads();
 #ifdef FBK_MM_STAMPS
@@ -615,41 +664,69 @@ __global__ void __launch_bounds__(256) k_icount_dense(const uint8_t* __restrict_
     st[3] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11));  // HW_REG_HW_ID
   }
 #endif
+  u64 tot = 0;
   if (threadIdx.x == 0) {
-    u64 tot = (u64)part[0] + part[1] + part[2] + part[3];
-    s_last = 0;
-    if (!total) {
-      if (kGroups == 1) out[pair] = tot;
-      else atomicAdd(&out[pair], tot);
-      // per-node reduce by accumulation: every block adds its count to *accum, which the caller
-      // zeroed beforehand — no ticket, no final pass, nothing serial behind the last workgroup
-      if (accum && tot) atomicAdd(accum, tot);
-    } else {
-      // Fused per-node reduce (executeCount's reduceFn, executor.go:5880): the block that
-      // finishes last sums the per-pair counts, so one step of the hot path is ONE launch.
-      // The blocks run on 8 XCDs with separate L2s: the count is published with an agent-scope
-      // atomic store (write-through, no L2-wide flush: a release FENCE here costs a full L2
-      // write-back per block and doubled the kernel time), completed before the ticket is taken.
-      if (kGroups == 1) __hip_atomic_store(&out[pair], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else atomicAdd(&out[pair], tot);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      s_last = (atomicAdd(done, 1u) == gridDim.x - 1) ? 1u : 0u;
+    tot = (u64)part[0] + part[1] + part[2] + part[3];
+    dense_publish<kGroups == 1>(&out[pair], tot, total != nullptr);
+  }
+  dense_block_tail(tot, out, total, done, n_pairs, accum);
+}
+
+// The same count for a plan whose rows the Infinity Cache can hold and which ran last on its context (plan_icount_enqueue_locked
+// decides): plain loads, so that the lines are allocated in L3 and the next launch finds them there, and a persistent grid —
+// block `bid` takes the pairs bid, bid + grid, ...  A launch with `rev` set is the mirror in time of one without: every block
+// walks its pairs last to first, the 4 KiB chunks of a row last to first and B before A, so that what the launch before read
+// LAST is read FIRST, while it is still resident (profiles/dense_resident.txt; the map (block, iteration, rev) -> pair is resident_pair, fbk_dense_policy.h).  kStream puts the non-temporal hint back: the
+// harness's control (scripts/dense_resident.hip), never instantiated by the library.
+template <bool kStream, bool kRev>
+__device__ __forceinline__ uint32_t dense_row_popcount(const ulonglong2* __restrict__ a, const ulonglong2* __restrict__ b) {
+  constexpr int kIters = kSlots * 8192 / 16 / 256, kUnroll = 8;
+  uint32_t c = 0;
+  for (int i0 = 0; i0 < kIters; i0 += kUnroll) {
+    ulonglong2 va[kUnroll], vb[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int ch = kRev ? kIters - 1 - (i0 + u) : i0 + u;
+      va[u] = kStream ? ld_stream(&a[ch * 256 + threadIdx.x]) : a[ch * 256 + threadIdx.x];
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int ch = kRev ? kIters - 1 - (i0 + u) : i0 + u;
+      vb[u] = kStream ? ld_stream(&b[ch * 256 + threadIdx.x]) : b[ch * 256 + threadIdx.x];
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) c += __popcll(va[u].x & vb[u].x) + __popcll(va[u].y & vb[u].y);
+  }
+  return c;
+}
+
+template <bool kStream = false>
+__global__ void __launch_bounds__(256) k_icount_dense_resident(const uint8_t* __restrict__ arenaA,
+                                                              const uint32_t* __restrict__ rowsA,
+                                                              const uint8_t* __restrict__ arenaB,
+                                                              const uint32_t* __restrict__ rowsB,
+                                                              u64* __restrict__ out, u64* __restrict__ total,
+                                                              uint32_t* __restrict__ done, uint32_t n_pairs,
+                                                              u64* __restrict__ accum, uint32_t rev) {
+  const uint64_t rowBytes = (uint64_t)kSlots * 8192;
+  const uint32_t n_it = resident_block_pairs(blockIdx.x, gridDim.x, n_pairs);
+  __shared__ uint32_t part[2][4];  // by the parity of the iteration: one barrier per pair
+  u64 blk = 0;
+  for (uint32_t it = 0; it < n_it; ++it) {
+    const uint32_t pair = resident_pair(blockIdx.x, gridDim.x, it, n_it, rev != 0u);
+    const ulonglong2* a = reinterpret_cast<const ulonglong2*>(arenaA + rowsA[pair] * rowBytes);
+    const ulonglong2* b = reinterpret_cast<const ulonglong2*>(arenaB + rowsB[pair] * rowBytes);
+    uint32_t c = rev ? dense_row_popcount<kStream, true>(b, a) : dense_row_popcount<kStream, false>(a, b);
+    c = wave_reduce_add(c);
+    if ((threadIdx.x & 63) == 0) part[it & 1u][threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const u64 tot = (u64)part[it & 1u][0] + part[it & 1u][1] + part[it & 1u][2] + part[it & 1u][3];
+      dense_publish<true>(&out[pair], tot, total != nullptr);
+      blk += tot;
     }
   }
-  if (!total) return;
-  __syncthreads();
-  if (!s_last) return;
-  u64 acc = 0;  // agent-scope loads: straight from the coherence point, no stale L2 lines
-  for (uint32_t i = threadIdx.x; i < n_pairs; i += 256) acc += __hip_atomic_load(&out[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, kWave);
-  __shared__ u64 tpart[4];
-  if ((threadIdx.x & 63) == 0) tpart[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    *total = tpart[0] + tpart[1] + tpart[2] + tpart[3];
-    *done = 0;  // ready for the next launch (stream ordered)
-  }
+  dense_block_tail(blk, out, total, done, n_pairs, accum);
 }
 
 // A <op> B for dense rows, materialised as dense rows, cardinality fused in the same
