@@ -1982,6 +1982,7 @@ int32_t fbk_setop(fbk_ctx* ctx, int32_t op, const fbk_batch* a, const uint32_t* 
 #include "fbk_quantile_api.inc"
 #include "fbk_distinct_rows_api.inc"
 #include "fbk_prepared_api.inc"
+#include "fbk_wire_parse.h"
 #include "fbk_wire_api.inc"
 #include "fbk_cache_api.inc"
 #include "fbk_group_api.inc"

@@ -13,7 +13,10 @@ The rest of the entry points are fuzzed in
   tests/test_gpu_fuzz_prepared.py  the prepared forms (fbk_query_*, fbk_plan_*): schedules of runs, reads, rewritten and compacted inputs,
                                    changed options, chains of row-valued queries — the state kept between launches
   tests/fuzz_prepared_gen.py       its case generator and model (no GPU)
-  tests/test_fuzz_prepared_cpu.py  the generator, the model against the oracle, and the coverage of the default iterations (no GPU)"""
+  tests/test_fuzz_prepared_cpu.py  the generator, the model against the oracle, and the coverage of the default iterations (no GPU)
+  tests/test_gpu_fuzz_wire.py  the serialised uploads (roaring images, the ops-log replay, RBF files): valid images and mutants of them
+  tests/wire_fuzz_gen.py       its case generator: images with their bit sets, tagged mutants, the oracle's verdict (no GPU)
+  tests/test_wire_fuzz_cpu.py  the host parsers over the same corpus under the sanitizers, and the coverage of the default iterations (no GPU)"""
 import os
 
 import numpy as np
