@@ -21,9 +21,6 @@
 
 #include "fbk_kernels.hip.h"
 #include "fbk_pair_kernels.hip.h"
-#ifdef FBK_EXPERIMENTS
-#include "fbk_pair_ring.hip.h"  // k_icount3 (round 6): parity-green and 1.5 x SLOWER than k_icount2 — kept as an experiment, not shipped
-#endif
 #include "fbk_query_kernels.hip.h"
 #include "fbk_fold_kernels.hip.h"
 #include "fbk_topk_kernels.hip.h"
@@ -152,15 +149,8 @@ struct FbkOptions {
 #ifdef FBK_EXPERIMENTS
   int64_t pair_stamp = 0;                // timing experiment on k_icount2: waves report shader cycles of a phase instead of counts (WRONG results)
   int64_t pair_ablate = 0;               // timing experiments on k_icount2 (skips parts of it: WRONG results)
-  int64_t pair_spw = 1;                  // experiment: container slots per wave of k_icount2 (1 | 2 | 4): the next slot's first payload batch is in flight while the current one is decoded
 #endif
-  int64_t pair_kernels = 0;              // 2: type-pair specialised k_icount2 / k_setop2 (one LDS clear per pair, probing); 1: the round-2 kernels; 0: by the rows' average payload (use_pair_kernels2); experiments builds only: 3 = the persistent loader / decoder count k_icount3 (fbk_pair_ring.hip.h; set-ops as 2)
-#ifdef FBK_EXPERIMENTS
-  int64_t ring_geom = 0;                 // k_icount3's block: 0 = 10 decoders + 64 KiB ring, one block per CU; 1 = 8 decoders; 2 = 6 decoders; 3 = 5 decoders + 32 KiB ring, two blocks per CU
-  int64_t ring_nt = 0;                   //   1: the payload DMAs carry the non-temporal hint
-  int64_t ring_flags = 0;                //   experiments on k_icount3 (bit 0: ring space is released after the decode)
-  int64_t ring_debug = 0;                //   1: every block reports the cycles its loader and decoders spent waiting; the averages go to stderr after each launch (which is then synchronous)
-#endif
+  int64_t pair_kernels = 0;              // 2: type-pair specialised k_icount2 / k_setop2 (one LDS clear per pair, probing); 1: the round-2 kernels; 0: by the rows' average payload (use_pair_kernels2)
 };
 
 struct fbk_ctx {
@@ -217,7 +207,7 @@ struct fbk_ctx {
   std::vector<struct fbk_cache_entry*> cache_zombies;  // invalidated while pinned
   uint64_t cache_bytes = 0, cache_cap_bytes = 128ull << 30, cache_clock = 0;
   uint64_t cache_hits = 0, cache_misses = 0, cache_evictions = 0;
-  // The plan whose dense count was the last device work of any size this context enqueued (plan_icount_enqueue_locked): its
+  // The plan whose dense count was the last device work of any size this context enqueued (plan_icount_dense, fbk_plan_api.inc): its
   // next count finds the rows in the Infinity Cache and takes k_icount_dense_resident.  Written under `mu`, cleared without
   // it by every entry point that is not quiet (FBK_ENTER); while such a call is in flight no plan becomes hot.
   std::atomic<const fbk_plan*> hot_plan{nullptr};
@@ -252,9 +242,6 @@ struct fbk_batch {
   std::mutex slots_mu;  // refresh_slots: h_slots / slots_stale
   uint64_t version = 0;  // bumped whenever the device descriptors are rewritten (a plan's resolved item records follow it)
   bool borrowed = false;  // the output of a plan / prepared query: owned by it and rewritten in place (n_rows x 16 cells of 8 KiB) by its next run
-  // every sparse container fits a k_icount3 decoder's registers (arrays <= 4096 values, run lists <= 2048 intervals); false = not
-  // known: uploads check their descriptors, kernel outputs are 8 KiB cells.  Batches that are not go to k_icount2.
-  bool ring_regular = false;
 };
 namespace {
 void ctx_loud_enter(fbk_ctx* ctx) {
@@ -263,7 +250,6 @@ void ctx_loud_enter(fbk_ctx* ctx) {
 }
 void ctx_loud_leave(fbk_ctx* ctx) { ctx->loud_calls.fetch_sub(1); }
 }  // namespace
-inline bool ring_fits(uint32_t type, uint32_t len) { return !((type == fbk::kTypeArray && len > 4096u) || (type == fbk::kTypeRun && len > 2048u)); }
 
 namespace {
 
@@ -416,13 +402,15 @@ struct DevBuf {
   // queued on it finishes before the block's next user starts.
   hipError_t ensure(fbk_ctx* ctx, uint64_t bytes) {
     if (p && cap >= bytes) return hipSuccess;
-    if (p) ctx_free(c, p);
-    p = nullptr;
+    reset();
     return alloc(ctx, bytes);
   }
-  ~DevBuf() {
+  void reset() {
     if (p) ctx_free(c, p);
+    p = nullptr;
+    cap = 0;
   }
+  ~DevBuf() { reset(); }
   template <class T>
   T* as() {
     return static_cast<T*>(p);
@@ -782,17 +770,10 @@ const OptionDesc kOptions[] = {
     {"upload_threads", &FbkOptions::upload_threads, 0, 64},
     {"upload_chunk_mb", &FbkOptions::upload_chunk_mb, 1, 1024},
     {"setop_direct_encode", &FbkOptions::setop_direct_encode, 0, 2},
-#ifndef FBK_EXPERIMENTS
     {"pair_kernels", &FbkOptions::pair_kernels, 0, 2},
-#else
-    {"pair_kernels", &FbkOptions::pair_kernels, 0, 3},
-    {"ring_geom", &FbkOptions::ring_geom, 0, 3},
-    {"ring_nt", &FbkOptions::ring_nt, 0, 1},
-    {"ring_debug", &FbkOptions::ring_debug, 0, 1},
-    {"ring_flags", &FbkOptions::ring_flags, 0, 255},
+#ifdef FBK_EXPERIMENTS
     {"pair_ablate", &FbkOptions::pair_ablate, 0, 4095},
     {"pair_stamp", &FbkOptions::pair_stamp, 0, 4},
-    {"pair_spw", &FbkOptions::pair_spw, 1, 4},
 #endif
     {"pair_wpb", &FbkOptions::pair_wpb, 0, 4},
     {"setop_compact", &FbkOptions::setop_compact, 0, 1},
@@ -1148,9 +1129,6 @@ static int32_t batch_upload_impl(fbk_ctx* ctx, const fbk_container_desc* descs, 
   }
   b->arena_bytes = off;
   b->dense = dense;
-  b->ring_regular = true;
-  for (uint64_t s = 0; s < n_slots; ++s)
-    if (src[s] >= 0 && !ring_fits(fbk::slot_type(b->h_slots[s]), b->h_slots[s].len)) b->ring_regular = false;
   // the arena image in (row, slot) order: payload bytes, then zeros up to the next 16-byte boundary
   struct Piece {
     uint64_t at, bytes, src;
@@ -1244,7 +1222,6 @@ int32_t fbk_batch_upload_dense(fbk_ctx* ctx, const uint64_t* words, uint32_t n_r
   b->n_rows = n_rows;
   b->arena_bytes = bytes;
   b->dense = n_rows > 0;
-  b->ring_regular = true;
   b->h_slots.resize(n_slots);
   b->h_keys.resize(n_slots);
   for (uint64_t s = 0; s < n_slots; ++s) {
@@ -1405,574 +1382,10 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 } FBK_ABI_CATCH(ctx)
 
 
-// ---- plans ---------------------------------------------------------------------------
-// A plan is a prepared list of row pairs (A.rows_a[i], B.rows_b[i]) whose index arrays and
-// output buffers live on the device, so that the hot path is launch-only: no host
-// allocation, no H2D copy, no synchronisation between steps.  It is the unit one
-// (query, node) batch call from mapperLocal (executor.go:6742) becomes.
-
 }  // extern "C"
 
 #include "fbk_output.inc"
-
-struct fbk_plan {
-  fbk_ctx* ctx = nullptr;
-  const fbk_batch* a = nullptr;
-  const fbk_batch* b = nullptr;
-  uint64_t n_pairs = 0;
-  uint32_t* d_rows_a = nullptr;
-  uint32_t* d_rows_b = nullptr;
-  u64* d_counts = nullptr;     // n_pairs (owned unless ext_counts)
-  u64* d_total = nullptr;      // 1
-  uint32_t* d_done = nullptr;  // ticket counter of the fused count + total kernel (kept at 0 between launches)
-  bool ext_counts = false;
-  fbk_batch* out = nullptr;    // lazily created by the first set-op enqueue
-  uint32_t* d_runs = nullptr;  // per output slot run count (optimize pass)
-  std::vector<uint32_t> h_rows_a, h_rows_b;
-  // k_icount2: the (pair, slot) item records resolved once per plan (re-resolved when a batch's descriptors were
-  // rewritten since) and one count per wave, summed per pair by k_sum_wave_counts
-  Slot* d_items = nullptr;
-  uint32_t* d_wave_counts = nullptr;
-  uint32_t* d_ring_ctl = nullptr;  // k_icount3: word 0 is OR-ed with 1 by a block that gave up on a wait (never in a correct run; fbk_plan_read reports it)
-  uint64_t items_va = ~0ull, items_vb = ~0ull;
-  bool last_rev = false;  // direction of the plan's last dense count (k_icount_dense_resident's `rev`; the cold kernel counts as forward)
-};
-
-namespace {
-
-// Average encoded payload per container of a batch, in bytes.
-uint64_t batch_avg_payload(const fbk_batch* b) {
-  const uint64_t slots = uint64_t(b->n_rows) * fbk::kSlots;
-  return slots ? b->arena_bytes / slots : 0;
-}
-// Which generation of the pair kernels a launch uses (option pair_kernels pins it: 1 / 2; 0 decides by the rows).
-// Rows of tiny containers on BOTH sides (arrays of a few values, a handful of runs) are served better by the round-2
-// kernels: there the launch of a block per item is what a kernel costs, not decode work or latency (BenchmarkCtOps
-// matrix, profiles/ctops_r03.txt: Ary16 x Ary16 10.5 us with k_icount, 18 us with k_icount2).
-bool use_pair_kernels2(const fbk_ctx* ctx, const fbk_batch* a, const fbk_batch* b, int op /* -1: count */) {
-  if (ctx->opt.pair_kernels) return ctx->opt.pair_kernels >= 2;
-  const uint64_t lo = std::min(batch_avg_payload(a), batch_avg_payload(b)), both = (a->arena_bytes + b->arena_bytes);
-  const uint64_t slots = (uint64_t(a->n_rows) + b->n_rows) * fbk::kSlots;
-  if (op >= 0) {
-    // materialising operations (8 KiB written per pair whatever the operands): k_setop2 wins where at least one side
-    // holds KiB-sized SPARSE containers — arrays from ~1000 values, long run lists — whose decode and load latency it
-    // was built around (Ary4096 x Ary1 XOR 73 -> 53 us; config 3's rows 89 -> 69 us); with small arrays on one side and
-    // small arrays or bitmaps on the other the round-2 kernel's cheaper per-item path is 10-25 % ahead
-    // (BenchmarkCtOps matrix, profiles/ctops_r03.txt)
-    const uint64_t big_sparse = std::max(a->dense ? 0 : batch_avg_payload(a), b->dense ? 0 : batch_avg_payload(b));
-    return big_sparse >= 1536;
-  }
-  if (!slots || both < 256 * slots) return false;
-  // one side tiny: when the other one is all bitmaps (or there is nothing on one side at all) the items are probes of a
-  // few dwords in global memory in either generation, and the round-2 kernel's four-wave blocks launch faster
-  // (Ary1 x BM512 7.4 us vs 9.3); against big arrays / run lists the table + probe form wins (Ary4096 x Ary1 48 -> 27 us)
-  if (lo < 256 && (a->arena_bytes == 0 || b->arena_bytes == 0 || (batch_avg_payload(a) < 256 ? b->dense : a->dense))) return false;
-  return true;
-}
-// Waves per block of the round-3 pair kernels (option pair_wpb pins it).  One-wave blocks release a wave's LDS table the
-// moment IT ends, which is what heterogeneous items (runs next to arrays) need; when one side's containers are tiny the
-// items are all alike and short, and four waves per block quarter the number of blocks to launch.
-int pair_wpb_for(const fbk_ctx* ctx, const fbk_batch* a, const fbk_batch* b) {
-  if (ctx->opt.pair_wpb) return ctx->opt.pair_wpb >= 4 ? 4 : 1;  // (normalised once: 1 or 4.  Two-wave blocks were built and measured in round 4: count 182 against 166-173 us, set-ops equal — profiles/r04_pairs_wpb_ab.json — and removed)
-  return std::min(batch_avg_payload(a), batch_avg_payload(b)) < 256 ? 4 : 1;
-}
-
-// The plan's item records: {A's descriptor, B's descriptor} per (pair, slot), resolved on the device once per version of the
-// two batches (k_resolve_items) — the pair kernels then start with ONE scalar round trip instead of row index -> descriptor.
-// Allocated with the per-wave count vector of the count kernel: both buffers or neither (a plan that got only the first, out
-// of memory on the second, must not take the resolved path next time).
-int32_t plan_resolve_items(fbk_ctx* ctx, fbk_plan* p) {
-  const uint64_t n_items = p->n_pairs * fbk::kSlots;
-  if (!p->d_items || !p->d_wave_counts) {
-    Slot* di = nullptr;
-    uint32_t* dw = nullptr;
-    HIP_TRY(ctx_malloc(ctx, reinterpret_cast<void**>(&di), std::max<uint64_t>(n_items, 1) * 2 * sizeof(Slot)));
-    if (hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&dw), std::max<uint64_t>(n_items, 1) * sizeof(uint32_t)); e != hipSuccess) {
-      ctx_free(ctx, di);
-      HIP_TRY(e);
-    }
-    p->d_items = di;
-    p->d_wave_counts = dw;
-    p->items_va = p->items_vb = ~0ull;
-  }
-  if (n_items && (p->items_va != p->a->version || p->items_vb != p->b->version)) {
-    hipLaunchKernelGGL(fbk::k_resolve_items, dim3(uint32_t((n_items + 255) / 256)), dim3(256), 0, ctx->stream, p->a->d_slots, p->d_rows_a, p->b->d_slots,
-                       p->d_rows_b, p->n_pairs, p->d_items);
-    HIP_TRY(hipGetLastError());
-    p->items_va = p->a->version;
-    p->items_vb = p->b->version;
-  }
-  return FBK_OK;
-}
-
-template <int OP>
-void launch_setop(bool dense, fbk_plan* p, hipStream_t st, bool want_runs, const Slot* items) {
-  const uint32_t blocks = uint32_t(p->n_pairs * fbk::kSlots / 4);
-  // (the in-kernel optimize() — mode 2 — only when the caller asked for optimize(): plain set-ops keep their bitmap cells)
-  const uint32_t direct = want_runs ? uint32_t(p->ctx->opt.setop_direct_encode) : 0u;
-#ifdef FBK_EXPERIMENTS  // (option pair_ablate, timing experiments on k_setop2: item classes skipped, emission without its stores — WRONG results)
-  const uint32_t direct2 = direct | 0x100u | (uint32_t(p->ctx->opt.pair_ablate) << 16);
-#else
-  const uint32_t direct2 = direct | 0x100u;  // k_setop2 only: Intersect / Difference whose result is a subset of an array operand by table + probe (an A/B option until round 5)
-#endif
-  if (dense)
-    hipLaunchKernelGGL(fbk::k_setop_dense<OP>, dim3(blocks), dim3(256), 0, st, p->a->d_arena, p->d_rows_a,
-                       p->b->d_arena, p->d_rows_b, p->out->d_arena, p->out->d_slots);
-  else if (use_pair_kernels2(p->ctx, p->a, p->b, OP == 0 ? FBK_OP_AND : OP == 1 ? FBK_OP_OR : OP == 2 ? FBK_OP_XOR : FBK_OP_ANDNOT) && pair_wpb_for(p->ctx, p->a, p->b) == 4)
-    hipLaunchKernelGGL((fbk::k_setop2<OP, 4>), dim3(blocks), dim3(256), 0, st, p->a->d_slots, p->a->d_arena, p->d_rows_a,
-                       p->b->d_slots, p->b->d_arena, p->d_rows_b, p->n_pairs, p->out->d_arena, p->out->d_slots,
-                       want_runs ? p->d_runs : nullptr, direct2, (const Slot*)nullptr);
-  else if (use_pair_kernels2(p->ctx, p->a, p->b, OP == 0 ? FBK_OP_AND : OP == 1 ? FBK_OP_OR : OP == 2 ? FBK_OP_XOR : FBK_OP_ANDNOT))
-  {
-    // Intersect / Difference with optimize(): most results come from the probe paths — the register-lean instance (18 instead of 16 waves per CU;
-    // setop_direct_encode = 0 / 1 run the common instance + the separate re-encode pass: the byte-for-byte cross-check).  Union / Xor with
-    // optimize() send every item down the general path: there the lean instance loses 3 % (509 -> 524 us, profiles/r06_setop2_occupancy.txt)
-    constexpr bool kHasProbe = OP == 0 || OP == 3;
-    if (kHasProbe && direct == 2u)
-      hipLaunchKernelGGL((fbk::k_setop2<OP, 1, kHasProbe>), dim3(uint32_t(p->n_pairs * fbk::kSlots)), dim3(64), 0, st, p->a->d_slots, p->a->d_arena, p->d_rows_a,
-                         p->b->d_slots, p->b->d_arena, p->d_rows_b, p->n_pairs, p->out->d_arena, p->out->d_slots,
-                         want_runs ? p->d_runs : nullptr, direct2, items);
-    else
-      hipLaunchKernelGGL((fbk::k_setop2<OP, 1>), dim3(uint32_t(p->n_pairs * fbk::kSlots)), dim3(64), 0, st, p->a->d_slots, p->a->d_arena, p->d_rows_a,
-                         p->b->d_slots, p->b->d_arena, p->d_rows_b, p->n_pairs, p->out->d_arena, p->out->d_slots,
-                         want_runs ? p->d_runs : nullptr, direct2, items);
-  }
-  else
-    hipLaunchKernelGGL(fbk::k_setop<OP>, dim3(blocks), dim3(256), 0, st, p->a->d_slots, p->a->d_arena, p->d_rows_a,
-                       p->b->d_slots, p->b->d_arena, p->d_rows_b, p->n_pairs, p->out->d_arena, p->out->d_slots,
-                       want_runs ? p->d_runs : nullptr, direct);
-}
-
-void free_plan_storage(fbk_plan* p) {
-  if (!p) return;
-  if (p->d_rows_a) (void)ctx_free(p->ctx, p->d_rows_a);
-  if (p->d_rows_b) (void)ctx_free(p->ctx, p->d_rows_b);
-  if (p->d_counts && !p->ext_counts) (void)ctx_free(p->ctx, p->d_counts);
-  if (p->d_total) (void)ctx_free(p->ctx, p->d_total);
-  if (p->d_done) (void)ctx_free(p->ctx, p->d_done);
-  if (p->d_runs) (void)ctx_free(p->ctx, p->d_runs);
-  if (p->d_items) (void)ctx_free(p->ctx, p->d_items);
-  if (p->d_wave_counts) (void)ctx_free(p->ctx, p->d_wave_counts);
-  if (p->d_ring_ctl) (void)ctx_free(p->ctx, p->d_ring_ctl);
-  free_batch_storage(p->out);
-  const fbk_plan* self = p;
-  if (p->ctx) p->ctx->hot_plan.compare_exchange_strong(self, nullptr);  // (a later plan may get this address)
-  delete p;
-}
-
-int32_t plan_create_locked(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, const fbk_batch* b,
-                           const uint32_t* rows_b, uint64_t n_pairs, void* ext_counts, fbk_plan** out_plan) {
-  if (n_pairs > (1ull << 27)) return fail(FBK_E_INVALID, "too many pairs in one plan");
-  for (uint64_t i = 0; i < n_pairs; ++i)
-    if (rows_a[i] >= a->n_rows || rows_b[i] >= b->n_rows) return fail(FBK_E_INVALID, "row index out of range");
-  fbk_plan* p = new (std::nothrow) fbk_plan();
-  if (!p) return fail(FBK_E_NOMEM, "host allocation failed");
-  p->ctx = ctx;
-  p->a = a;
-  p->b = b;
-  p->n_pairs = n_pairs;
-  p->h_rows_a.assign(rows_a, rows_a + n_pairs);
-  p->h_rows_b.assign(rows_b, rows_b + n_pairs);
-  const uint64_t rb = std::max<uint64_t>(n_pairs, 1) * sizeof(uint32_t);
-  hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&p->d_rows_a), rb);
-  if (e == hipSuccess) e = ctx_malloc(ctx, reinterpret_cast<void**>(&p->d_rows_b), rb);
-  if (e == hipSuccess) e = ctx_malloc(ctx, reinterpret_cast<void**>(&p->d_total), sizeof(u64));
-  if (e == hipSuccess) e = ctx_malloc(ctx, reinterpret_cast<void**>(&p->d_done), sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemsetAsync(p->d_done, 0, sizeof(uint32_t), ctx->stream);
-  if (e == hipSuccess) {
-    if (ext_counts) {
-      p->d_counts = static_cast<u64*>(ext_counts);
-      p->ext_counts = true;
-    } else {
-      e = ctx_malloc(ctx, reinterpret_cast<void**>(&p->d_counts), std::max<uint64_t>(n_pairs, 1) * sizeof(u64));
-    }
-  }
-  if (e == hipSuccess && n_pairs) {
-    e = hipMemcpyAsync(p->d_rows_a, rows_a, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->d_rows_b, rows_b, n_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    free_plan_storage(p);
-    return fail(e == hipErrorOutOfMemory ? FBK_E_NOMEM : FBK_E_HIP, std::string("plan: ") + hipGetErrorString(e));
-  }
-  *out_plan = p;
-  return FBK_OK;
-}
-
-int32_t plan_icount_enqueue_locked(fbk_ctx* ctx, fbk_plan* p, u64* fused_total = nullptr, u64* accum = nullptr) {
-  if (p->n_pairs == 0) {
-    if (fused_total) HIP_TRY(hipMemsetAsync(fused_total, 0, sizeof(u64), ctx->stream));
-    return FBK_OK;
-  }
-  const uint32_t np = uint32_t(p->n_pairs);
-  if (p->a->dense && p->b->dense) {
-    // all-bitmap rows: pure streaming kernel.  slots-per-block 16 = one block per row
-    // pair, plain store; smaller groups = more blocks + one atomicAdd per block.
-    const int spb = int(ctx->opt.dense_spb);
-    // A plan whose rows the Infinity Cache can hold, counted again with nothing else enqueued on the context in between
-    // (hot_plan): the rows are where the last launch left them, and k_icount_dense_resident reads them in the reverse
-    // of that launch's order — what was read last, and is surest to be resident still, first.  Everything else, the
-    // plan's first count included, is cold data to this context: the non-temporal kernel below, unchanged.
-    // (Not seen from here: other contexts, forks and processes on the device.  A hot launch after they evicted the rows
-    // reads HBM with plain loads — DESIGN.md §9 has the cost.)
-    const bool hot = spb == 16 && ctx->hot_plan.load() == p &&
-                     fbk::dense_footprint_bound(p->n_pairs, p->a->n_rows, p->b->n_rows, p->a == p->b) <= fbk::kDenseResidentMaxBytes;
-    if (hot) {
-      // one block per compute unit: at 256 MiB 35.0 us against 38.1-39.5 with two to four (and 41.5 for the non-temporal kernel) —
-      // the fewer blocks walk the rows at a time, the closer a launch is to the mirror of the one before (profiles/dense_resident.txt)
-      const uint32_t grid = std::min<uint32_t>(np, uint32_t(ctx->n_cu > 0 ? ctx->n_cu : 256));
-      p->last_rev = !p->last_rev;
-      hipLaunchKernelGGL(fbk::k_icount_dense_resident<false>, dim3(grid), dim3(256), 0, ctx->stream, p->a->d_arena, p->d_rows_a, p->b->d_arena,
-                         p->d_rows_b, p->d_counts, fused_total, p->d_done, np, accum, p->last_rev ? 1u : 0u);
-      HIP_TRY(hipGetLastError());
-      return FBK_OK;  // (still the context's hot plan)
-    }
-    if (spb != 16) HIP_TRY(hipMemsetAsync(p->d_counts, 0, p->n_pairs * sizeof(u64), ctx->stream));
-#define FBK_LAUNCH_DENSE(S)                                                                                       \
-  hipLaunchKernelGGL(fbk::k_icount_dense<S>, dim3(np*(16 / S)), dim3(256), 0, ctx->stream, p->a->d_arena,         \
-                     p->d_rows_a, p->b->d_arena, p->d_rows_b, p->d_counts, fused_total, p->d_done, np, accum)
-    switch (spb) {
-      case 1: FBK_LAUNCH_DENSE(1); break;
-      case 2: FBK_LAUNCH_DENSE(2); break;
-      case 4: FBK_LAUNCH_DENSE(4); break;
-      case 8: FBK_LAUNCH_DENSE(8); break;
-      default: FBK_LAUNCH_DENSE(16); break;
-    }
-#undef FBK_LAUNCH_DENSE
-    HIP_TRY(hipGetLastError());
-    // the plan is hot from here on, unless a call that is not quiet is running on the context right now (another thread's:
-    // whatever it enqueues may come after this launch)
-    p->last_rev = false;
-    ctx->hot_plan.store(p);
-    if (ctx->loud_calls.load() != 0) ctx->hot_plan.store(nullptr);
-    return FBK_OK;
-  } else {
-    ctx->hot_plan.store(nullptr);  // (the count entry points are quiet: a count over encoded rows ends a dense plan's residency here)
-    const bool pk2 = use_pair_kernels2(ctx, p->a, p->b, -1);
-#ifdef FBK_EXPERIMENTS
-    const bool pk3 = ctx->opt.pair_kernels == 3 && p->a->ring_regular && p->b->ring_regular;
-#else
-    constexpr bool pk3 = false;
-#endif
-    // (resolved item records + a count per wave pay for their second launch only where the items are heavy: one-wave blocks)
-    const bool resolved = pk3 || (pk2 && pair_wpb_for(ctx, p->a, p->b) == 1);
-    if (!resolved) HIP_TRY(hipMemsetAsync(p->d_counts, 0, p->n_pairs * sizeof(u64), ctx->stream));
-    if (resolved)
-      if (int32_t rc = plan_resolve_items(ctx, p)) return rc;
-#ifdef FBK_EXPERIMENTS
-    if (pk3) {
-      // the persistent loader / decoder kernel: a block per compute unit (or two), every block walks its share of the item records
-      if (!p->d_ring_ctl) {
-        HIP_TRY(ctx_malloc(ctx, reinterpret_cast<void**>(&p->d_ring_ctl), 32));
-        HIP_TRY(hipMemsetAsync(p->d_ring_ctl, 0, 32, ctx->stream));
-      }
-      const uint64_t n_items = p->n_pairs * fbk::kSlots, n_chunks = (n_items + fbk::kRgChunk - 1) / fbk::kRgChunk;
-      const uint32_t cus = uint32_t(ctx->n_cu > 0 ? ctx->n_cu : 256);
-#define FBK_LAUNCH_ICOUNT3(D, R, NT, PER_CU)                                                                                                   \
-  hipLaunchKernelGGL((fbk::k_icount3<D, R, NT>), dim3(uint32_t(std::min<uint64_t>(n_chunks, uint64_t(cus) * PER_CU))), dim3(64 * (D + 1)), 0, \
-                     ctx->stream, p->d_items, p->a->d_arena, p->b->d_arena, n_items, p->d_wave_counts, p->d_ring_ctl, d_dbg, uint32_t(ctx->opt.ring_flags))
-      const bool nt = ctx->opt.ring_nt != 0;
-      const uint32_t per_cu = ctx->opt.ring_geom == 3 ? 2u : 1u;
-      const uint32_t dbg_blocks = uint32_t(std::min<uint64_t>(n_chunks, uint64_t(cus) * per_cu));
-      DevBuf dbgbuf;
-      uint32_t* d_dbg = nullptr;
-      if (ctx->opt.ring_debug) {
-        HIP_TRY(dbgbuf.alloc(ctx, uint64_t(dbg_blocks) * 32 * 4));
-        HIP_TRY(hipMemsetAsync(dbgbuf.p, 0, uint64_t(dbg_blocks) * 32 * 4, ctx->stream));
-        d_dbg = dbgbuf.as<uint32_t>();
-      }
-      switch (ctx->opt.ring_geom) {
-        case 1: if (nt) FBK_LAUNCH_ICOUNT3(8, 65536, true, 1); else FBK_LAUNCH_ICOUNT3(8, 65536, false, 1); break;
-        case 2: if (nt) FBK_LAUNCH_ICOUNT3(6, 65536, true, 1); else FBK_LAUNCH_ICOUNT3(6, 65536, false, 1); break;
-        case 3: if (nt) FBK_LAUNCH_ICOUNT3(5, 32768, true, 2); else FBK_LAUNCH_ICOUNT3(5, 32768, false, 2); break;
-        default: if (nt) FBK_LAUNCH_ICOUNT3(10, 65536, true, 1); else FBK_LAUNCH_ICOUNT3(10, 65536, false, 1); break;
-      }
-#undef FBK_LAUNCH_ICOUNT3
-      if (d_dbg) {
-        std::vector<uint32_t> h(uint64_t(dbg_blocks) * 32);
-        HIP_TRY(hipMemcpyAsync(h.data(), d_dbg, h.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        double sum[32] = {0};
-        uint32_t tmax = 0, tmin = ~0u;
-        for (uint32_t b = 0; b < dbg_blocks; ++b) {
-          for (int k = 0; k < 32; ++k) sum[k] += h[uint64_t(b) * 32 + k];
-          tmax = std::max(tmax, h[uint64_t(b) * 32]);
-          tmin = std::min(tmin, h[uint64_t(b) * 32]);
-        }
-        std::fprintf(stderr, "[ring_debug] blocks %u planner cycles avg %.0f min %u max %u | wait records %.0f slots %.0f | reclaim polls %.0f entries %.0f | decoders (summed per block): wait entry %.0f issue %.0f wait payload %.0f decode %.0f items %.0f deferred %.0f\n",
-                     dbg_blocks, sum[0] / dbg_blocks, tmin, tmax, sum[1] / dbg_blocks, sum[2] / dbg_blocks, sum[6] / dbg_blocks, sum[7] / dbg_blocks, sum[8] / dbg_blocks,
-                     sum[12] / dbg_blocks, sum[11] / dbg_blocks, sum[9] / dbg_blocks, sum[10] / dbg_blocks, sum[13] / dbg_blocks);
-        if (sum[21] > 0 && sum[26] > 0)
-          std::fprintf(stderr, "[ring_debug]   array x array phases, cycles per item: payload -> registers %.0f, take next %.0f, scatter %.0f, probe + reduce %.0f (dwords per item: table side %.0f, probing side %.0f)\n",
-                       sum[26] / sum[21], sum[27] / sum[21], sum[28] / sum[21], sum[29] / sum[21], sum[30] / sum[21], sum[31] / sum[21]);
-        static const char* kCls[5] = {"array x array", "array x bitmap", "array x run (<= 600)", "general (run x run, run x bitmap, long runs)", "outside the ring / bitmap x bitmap"};
-        for (int k = 0; k < 5; ++k)
-          if (sum[21 + k] > 0) std::fprintf(stderr, "[ring_debug]   %-48s items %8.0f  decode cycles per item %7.0f\n", kCls[k], sum[21 + k], sum[16 + k] / sum[21 + k]);
-      }
-      hipLaunchKernelGGL(fbk::k_sum_wave_counts, dim3(uint32_t((p->n_pairs + 255) / 256)), dim3(256), 0, ctx->stream, p->d_wave_counts,
-                         uint32_t(fbk::kSlots), p->n_pairs, p->d_counts, p->d_ring_ctl + 1);
-    } else
-#endif
-    if (pk2) {
-#define FBK_LAUNCH_ICOUNT2(S, W)                                                                                                   \
-  hipLaunchKernelGGL((fbk::k_icount2<S, W>), dim3(uint32_t((p->n_pairs * (fbk::kSlots / S) + W - 1) / W)), dim3(64 * W), 0, ctx->stream, \
-                     p->a->d_slots, p->a->d_arena, p->d_rows_a, p->b->d_slots, p->b->d_arena, p->d_rows_b, p->n_pairs,            \
-                     p->d_counts, pair_flags, resolved ? p->d_items : (const Slot*)nullptr,  \
-                     resolved ? p->d_wave_counts : (uint32_t*)nullptr)
-      // One container slot per wave.  (The kernel is written for SPW slots per wave with the next slot's payload in flight while the
-      // current one is decoded; SPW = 2 / 4 measured 49.6 / 56 us against 46 on 2048 row pairs in round 3 and 172 / 184 us against 157-162
-      // on 8192 in round 5 — profiles/r05_pairs_spw_8192_pairs.json: the same 6-10 % / 17-24 % behind at both sizes, so not a tail effect;
-      // a wave that decodes two items one after the other holds its table twice as long, and the second payload, requested before the
-      // first item's own later loads, has to land before those can be waited for (the vector memory counter is in order).  Instantiated in
-      // the experiments build only, option pair_spw there.)
-      const int wpb = pair_wpb_for(ctx, p->a, p->b);
-#ifdef FBK_EXPERIMENTS
-      const uint32_t pair_flags = 3u | (uint32_t(ctx->opt.pair_ablate & 255) << 8) | (uint32_t(ctx->opt.pair_stamp) << 16);
-#else
-      constexpr uint32_t pair_flags = 3u;  // bit 0: the small-array / probe paths, bit 1: array x run items probe the run container's table (both were A/B options until round 5)
-#endif
-      uint32_t spw = 1;
-      if (wpb == 4) FBK_LAUNCH_ICOUNT2(1, 4);
-#ifdef FBK_EXPERIMENTS
-      else if (ctx->opt.pair_spw == 4) { spw = 4; FBK_LAUNCH_ICOUNT2(4, 1); }
-      else if (ctx->opt.pair_spw == 2) { spw = 2; FBK_LAUNCH_ICOUNT2(2, 1); }
-#endif
-      else FBK_LAUNCH_ICOUNT2(1, 1);
-#undef FBK_LAUNCH_ICOUNT2
-      if (resolved)
-        hipLaunchKernelGGL(fbk::k_sum_wave_counts, dim3(uint32_t((p->n_pairs + 255) / 256)), dim3(256), 0, ctx->stream, p->d_wave_counts,
-                           uint32_t(fbk::kSlots) / spw, p->n_pairs, p->d_counts, (uint32_t*)nullptr);
-    }
-    else
-      hipLaunchKernelGGL(fbk::k_icount, dim3(np * (fbk::kSlots / 4)), dim3(256), 0, ctx->stream, p->a->d_slots,
-                         p->a->d_arena, p->d_rows_a, p->b->d_slots, p->b->d_arena, p->d_rows_b, p->n_pairs, p->d_counts,
-                         1u);
-    if (fused_total)
-      hipLaunchKernelGGL(fbk::k_sum_u64, dim3(1), dim3(256), 0, ctx->stream, p->d_counts, p->n_pairs, fused_total);
-    if (accum) hipLaunchKernelGGL(fbk::k_sum_u64_add, dim3(1), dim3(256), 0, ctx->stream, p->d_counts, p->n_pairs, accum);
-  }
-  HIP_TRY(hipGetLastError());
-  return FBK_OK;
-}
-
-int32_t plan_setop_enqueue_locked(fbk_ctx* ctx, fbk_plan* p, int32_t op, bool want_runs) {
-  const uint64_t n_slots = p->n_pairs * fbk::kSlots;
-  if (!p->out) {
-    // the output keys are derived from the inputs' host slot tables: refresh them if an input is
-    // itself the output of an asynchronous operation
-    if (int32_t rc = refresh_slots(const_cast<fbk_batch*>(p->a))) return rc;
-    if (int32_t rc = refresh_slots(const_cast<fbk_batch*>(p->b))) return rc;
-    if (int32_t rc = alloc_cell_batch(ctx, p->n_pairs, &p->out, "setop output")) return rc;
-    fbk_batch* o = p->out;
-    o->borrowed = true;
-    for (uint64_t i = 0; i < p->n_pairs; ++i)
-      for (int s = 0; s < fbk::kSlots; ++s) {
-        const uint64_t ia = uint64_t(p->h_rows_a[i]) * fbk::kSlots + s, ib = uint64_t(p->h_rows_b[i]) * fbk::kSlots + s;
-        // a nil/nil slot pair yields nil and its key is never reported
-        const bool has_a = fbk::slot_type(p->a->h_slots[ia]) != fbk::kTypeNil;
-        o->h_keys[i * fbk::kSlots + s] = has_a ? p->a->h_keys[ia] : p->b->h_keys[ib];
-      }
-  }
-  if (want_runs && !p->d_runs) HIP_TRY(ctx_malloc(ctx, reinterpret_cast<void**>(&p->d_runs), std::max<uint64_t>(n_slots, 1) * 4));
-  if (p->n_pairs == 0) return FBK_OK;
-  const bool dense = p->a->dense && p->b->dense && !want_runs;
-  // the one-wave-block pair kernels start from the plan's resolved item records (as the count does)
-  const Slot* items = nullptr;
-  if (!dense && use_pair_kernels2(ctx, p->a, p->b, op) && pair_wpb_for(ctx, p->a, p->b) == 1) {
-    if (int32_t rc = plan_resolve_items(ctx, p)) return rc;
-    items = p->d_items;
-  }
-  switch (op) {
-    case FBK_OP_AND: launch_setop<0>(dense, p, ctx->stream, want_runs, items); break;
-    case FBK_OP_OR: launch_setop<1>(dense, p, ctx->stream, want_runs, items); break;
-    case FBK_OP_XOR: launch_setop<2>(dense, p, ctx->stream, want_runs, items); break;
-    default: launch_setop<3>(dense, p, ctx->stream, want_runs, items); break;
-  }
-  // the pair's cardinality = the sum of the n its 16 output descriptors carry (rounds 1-3: a uint64 atomic per wave onto a
-  // zeroed vector; measured equal within 1 % on config 3's 8192 row pairs, and one launch instead of memset + atomics)
-  hipLaunchKernelGGL(fbk::k_sum_slot_n, dim3(uint32_t((p->n_pairs + 255) / 256)), dim3(256), 0, ctx->stream, p->out->d_slots, p->n_pairs, p->d_counts);
-  HIP_TRY(hipGetLastError());
-  // dense kernels write the dense layout (an all-zero result cell stays an all-zero
-  // bitmap in the arena, its slot says nil): the output can feed the dense kernels again
-  p->out->dense = dense;
-  slots_rewritten(p->out);
-  return FBK_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t fbk_plan_create(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, const fbk_batch* b,
-                        const uint32_t* rows_b, uint64_t n_pairs, void* device_counts_or_null, fbk_plan** out_plan) try {
-  FBK_ENTER(ctx);
-  if (!ctx || !a || !b || !out_plan || (n_pairs && (!rows_a || !rows_b))) return fail(FBK_E_INVALID, "NULL argument");
-  *out_plan = nullptr;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  return plan_create_locked(ctx, a, rows_a, b, rows_b, n_pairs, device_counts_or_null, out_plan);
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_free(fbk_ctx* ctx, fbk_plan* plan) try {
-  FBK_ENTER(ctx);
-  if (!plan) return FBK_OK;
-  if (!ctx) ctx = plan->ctx;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  free_plan_storage(plan);
-  return FBK_OK;
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_intersection_count(fbk_ctx* ctx, fbk_plan* plan) try {
-  FBK_ENTER_QUIET(ctx);
-  if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  return plan_icount_enqueue_locked(ctx, plan);
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_intersection_count_total(fbk_ctx* ctx, fbk_plan* plan, void* device_total_or_null) try {
-  FBK_ENTER_QUIET(ctx);
-  if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  u64* dst = device_total_or_null ? static_cast<u64*>(device_total_or_null) : plan->d_total;
-  return plan_icount_enqueue_locked(ctx, plan, dst);
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_intersection_count_accumulate(fbk_ctx* ctx, fbk_plan* plan, void* device_accum) try {
-  FBK_ENTER_QUIET(ctx);
-  if (!ctx || !plan || !device_accum) return fail(FBK_E_INVALID, "NULL argument");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  return plan_icount_enqueue_locked(ctx, plan, nullptr, static_cast<u64*>(device_accum));
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_setop(fbk_ctx* ctx, fbk_plan* plan, int32_t op, uint32_t flags) try {
-  FBK_ENTER(ctx);
-  if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
-  if (op < 0 || op > 3) return fail(FBK_E_INVALID, "unknown set operation");
-  if (flags & ~FBK_SETOP_OPTIMIZE) return fail(FBK_E_INVALID, "unknown flags");
-  const bool opt = (flags & FBK_SETOP_OPTIMIZE) != 0;
-  if (opt && ctx->opt.setop_direct_encode != 2)
-    return fail(FBK_E_INVALID, "FBK_SETOP_OPTIMIZE on a plan needs option setop_direct_encode = 2 (optimize() inside the kernel); the separate re-encode pass sizes its output on the host: use fbk_setop");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  return plan_setop_enqueue_locked(ctx, plan, op, opt);
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_total(fbk_ctx* ctx, fbk_plan* plan, void* device_total_or_null) try {
-  FBK_ENTER_QUIET(ctx);
-  if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  u64* dst = device_total_or_null ? static_cast<u64*>(device_total_or_null) : plan->d_total;
-  hipLaunchKernelGGL(fbk::k_sum_u64, dim3(1), dim3(256), 0, ctx->stream, plan->d_counts, plan->n_pairs, dst);
-  HIP_TRY(hipGetLastError());
-  return FBK_OK;
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_read(fbk_ctx* ctx, fbk_plan* plan, uint64_t* out_counts, uint64_t* out_total) try {
-  FBK_ENTER_QUIET(ctx);
-  if (!ctx || !plan) return fail(FBK_E_INVALID, "NULL argument");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  if (out_counts && plan->n_pairs)
-    HIP_TRY(hipMemcpyAsync(out_counts, plan->d_counts, plan->n_pairs * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-  if (out_total) HIP_TRY(hipMemcpyAsync(out_total, plan->d_total, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-  uint32_t ring_ctl[8] = {0};
-  if (plan->d_ring_ctl) HIP_TRY(hipMemcpyAsync(ring_ctl, plan->d_ring_ctl, sizeof(ring_ctl), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  if (ring_ctl[0]) {
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), "k_icount3: a block gave up on a wait (protocol error): the counts of this plan are not valid [where %u block %u wave %u: %u %u %u | pub %u tail %u]",
-                  ring_ctl[2] & 255u, (ring_ctl[2] >> 8) & 0xFFFFu, ring_ctl[2] >> 24, ring_ctl[3], ring_ctl[4], ring_ctl[5], ring_ctl[6], ring_ctl[7]);
-    return fail(FBK_E_HIP, buf);
-  }
-  return FBK_OK;
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_output(fbk_ctx* ctx, fbk_plan* plan, fbk_batch** out_batch) try {
-  FBK_ENTER(ctx);
-  if (!plan || !out_batch) return fail(FBK_E_INVALID, "NULL argument");
-  (void)ctx;
-  *out_batch = plan->out;
-  if (!plan->out) return fail(FBK_E_INVALID, "plan has no set-op output yet");
-  return FBK_OK;
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_plan_detach_output(fbk_ctx* ctx, fbk_plan* plan, fbk_batch** out_batch) try {
-  FBK_ENTER(ctx);
-  if (!plan || !out_batch) return fail(FBK_E_INVALID, "NULL argument");
-  if (!ctx) ctx = plan->ctx;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (!plan->out) return fail(FBK_E_INVALID, "plan has no set-op output yet");
-  *out_batch = plan->out;
-  plan->out->borrowed = false;  // the caller's from here on: nothing rewrites it in place any more (fbk_batch_compact accepts it)
-  plan->out = nullptr;
-  return FBK_OK;
-} FBK_ABI_CATCH(ctx)
-
-// ---- one-shot calls (plan + enqueue + read) --------------------------------------------
-
-int32_t fbk_intersection_count(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, const fbk_batch* b,
-                               const uint32_t* rows_b, uint64_t n_pairs, uint64_t* out_counts) try {
-  FBK_ENTER(ctx);
-  if (!ctx || !a || !b || (n_pairs && (!rows_a || !rows_b || !out_counts))) return fail(FBK_E_INVALID, "NULL argument");
-  if (n_pairs == 0) return FBK_OK;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  fbk_plan* p = nullptr;
-  if (int32_t rc = plan_create_locked(ctx, a, rows_a, b, rows_b, n_pairs, nullptr, &p)) return rc;
-  int32_t rc = plan_icount_enqueue_locked(ctx, p);
-  if (!rc) {
-    D2H back(ctx);
-    hipError_t e = back.add(out_counts, p->d_counts, n_pairs * sizeof(u64));
-    if (e == hipSuccess) e = back.finish();
-    if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("intersection_count: ") + hipGetErrorString(e));
-  }
-  (void)hipStreamSynchronize(ctx->stream);
-  free_plan_storage(p);
-  return rc;
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_setop(fbk_ctx* ctx, int32_t op, const fbk_batch* a, const uint32_t* rows_a, const fbk_batch* b,
-                  const uint32_t* rows_b, uint64_t n_pairs, uint32_t flags, fbk_batch** out_batch,
-                  uint64_t* out_counts) try {
-  FBK_ENTER(ctx);
-  if (!ctx || !a || !b || !out_batch || (n_pairs && (!rows_a || !rows_b))) return fail(FBK_E_INVALID, "NULL argument");
-  if (op < 0 || op > 3) return fail(FBK_E_INVALID, "unknown set operation");
-  if (flags & ~FBK_SETOP_OPTIMIZE) return fail(FBK_E_INVALID, "unknown flags");
-  *out_batch = nullptr;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  fbk_plan* p = nullptr;
-  if (int32_t rc = plan_create_locked(ctx, a, rows_a, b, rows_b, n_pairs, nullptr, &p)) return rc;
-  const bool opt = (flags & FBK_SETOP_OPTIMIZE) != 0;
-  int32_t rc = plan_setop_enqueue_locked(ctx, p, op, opt);
-  if (!rc && out_counts && n_pairs) {
-    hipError_t e = hipMemcpyAsync(out_counts, p->d_counts, n_pairs * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream);
-    if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("setop: ") + hipGetErrorString(e));
-  }
-  if (!rc && opt && ctx->opt.setop_direct_encode != 2) rc = optimize_cells(ctx, p->out, p->d_runs);  // (mode 2: the kernel has encoded already)
-  else if (!rc && opt && ctx->opt.setop_compact) rc = compact_cells(ctx, p->out);  // ... into the head of 8 KiB cells: the caller owns this batch, it gets a right-sized arena
-  if (!rc) rc = refresh_slots(p->out);
-  hipError_t e = hipStreamSynchronize(ctx->stream);
-  if (!rc && e != hipSuccess) rc = fail(FBK_E_HIP, std::string("setop: ") + hipGetErrorString(e));
-  if (!rc) {
-    *out_batch = p->out;
-    p->out->borrowed = false;
-    p->out = nullptr;
-  }
-  free_plan_storage(p);
-  return rc;
-} FBK_ABI_CATCH(ctx)
-
-}  // extern "C"
-
+#include "fbk_plan_api.inc"
 #include "fbk_dense_operands.inc"
 #include "fbk_query_api.inc"
 #include "fbk_matrix_sum_api.inc"

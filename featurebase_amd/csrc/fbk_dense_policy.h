@@ -1,5 +1,5 @@
-// fbk_dense_policy.h — shape rules of the dense count: which plans take k_icount_dense_resident (plan_icount_enqueue_locked,
-// fbk.hip) and which pairs a block of its persistent grid walks, in which order.  Plain C++, HIP not needed:
+// fbk_dense_policy.h — shape rules of the dense count: which plans take k_icount_dense_resident (plan_icount_dense,
+// fbk_plan_api.inc) and which pairs a block of its persistent grid walks, in which order.  Plain C++, HIP not needed:
 // scripts/dense_footprint_check.cpp compiles it on its own.
 #pragma once
 #include <stdint.h>

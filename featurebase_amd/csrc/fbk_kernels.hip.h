@@ -672,7 +672,7 @@ __global__ void __launch_bounds__(256) k_icount_dense(const uint8_t* __restrict_
   dense_block_tail(tot, out, total, done, n_pairs, accum);
 }
 
-// The same count for a plan whose rows the Infinity Cache can hold and which ran last on its context (plan_icount_enqueue_locked
+// The same count for a plan whose rows the Infinity Cache can hold and which ran last on its context (plan_icount_dense
 // decides): plain loads, so that the lines are allocated in L3 and the next launch finds them there, and a persistent grid —
 // block `bid` takes the pairs bid, bid + grid, ...  A launch with `rev` set is the mirror in time of one without: every block
 // walks its pairs last to first, the 4 KiB chunks of a row last to first and B before A, so that what the launch before read

@@ -22,7 +22,6 @@ int32_t alloc_cell_batch(fbk_ctx* ctx, uint64_t n_rows, fbk_batch** out, const c
   o->ctx = ctx;
   o->n_rows = uint32_t(n_rows);
   o->arena_bytes = n_slots * 8192ull;
-  o->ring_regular = true;  // (8 KiB cells)
   o->h_slots.assign(n_slots, Slot{0, 0, 0});
   o->h_keys.assign(n_slots, 0);
   // default keys: out_row * 16 + slot, the fragment-storage form (rowID << 4 | slot) with the output

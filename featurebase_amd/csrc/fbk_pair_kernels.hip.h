@@ -605,13 +605,14 @@ __device__ __forceinline__ void frag_load_pair(const Slot& sa, const uint8_t* __
 
 // ---- |A ∩ B| over row pairs, any mix of encodings (intersectionCount, roaring.go:4477-4614) -------------
 //
-// One WAVE = SPW consecutive slots of one row pair.  Everything that decides control flow is wave-uniform
-// and held in SCALAR registers: the wave index comes from v_readfirstlane, so the row indexes and the 2 x SPW
+// One WAVE = one slot of one row pair.  Everything that decides control flow is wave-uniform
+// and held in SCALAR registers: the wave index comes from v_readfirstlane, so the row indexes and the two
 // descriptors are s_loads (the round-2 kernel computed them per lane: four dependent VECTOR round trips —
 // row index, cardinality, offset / length, payload — before the first payload byte arrived, ~10 us of a
 // wave's life at five waves per SIMD; that chain, not the LDS, was what the 70 us of k_icount were made of)
-// and every loop has a uniform trip count.  The first payload batch of slot k + 1 is in flight while slot k
-// is worked on, and the wave adds ONE count to out[pair].
+// and every loop has a uniform trip count.  The wave adds ONE count to out[pair].
+// (SPW = 2 / 4 slots per wave, the next slot's first payload batch in flight while the current one is decoded, was built and lost
+// its A/B twice: 6-10 % / 17-24 % behind, profiles/r05_pairs_spw_2048_pairs.json and profiles/r05_pairs_spw_8192_pairs.json.)
 
 // batch 0 of both operands of an item, if the item will be decoded at all
 __device__ __forceinline__ void count_units(uint32_t ta, uint32_t la, uint32_t tb, uint32_t lb, uint32_t sparse_paths, uint32_t& ua, uint32_t& ub) {
@@ -776,26 +777,12 @@ __device__ __forceinline__ void icount_item(const Slot& sa, const uint8_t* __res
   }
 }
 
-// items K .. SPW - 1 of a wave, the next one's batch 0 in flight while item K is worked on (a template recursion:
-// the item body is too large for the unroller, and a real loop would index the descriptor arrays dynamically)
-template <int K, int SPW>
-__device__ __forceinline__ void icount_items(const Slot (&sa)[SPW], const uint8_t* __restrict__ arenaA, const Slot (&sb)[SPW],
-                                             const uint8_t* __restrict__ arenaB, int lane, u64* table, uint32_t* mini, uint32_t (&va)[kPairBatch],
-                                             uint32_t (&vb)[kPairBatch], uint32_t sparse_paths, uint32_t& part, uint32_t& spart) {
-  if constexpr (K < SPW) {
-    uint32_t xa[kPairBatch], xb[kPairBatch];
-    if constexpr (K + 1 < SPW) item_prefetch(sa[K + 1], arenaA, sb[K + 1], arenaB, lane, xa, xb, sparse_paths);
-    icount_item(sa[K], arenaA, sb[K], arenaB, lane, table, mini, va, vb, sparse_paths, part, spart);
-    if constexpr (K + 1 < SPW) icount_items<K + 1, SPW>(sa, arenaA, sb, arenaB, lane, table, mini, xa, xb, sparse_paths, part, spart);
-  }
-}
-
 // WPB waves per block.  A block's LDS and wave slots are released when its LAST wave ends, and an item with a run
 // lives several times as long as an array x array one: with four waves per block 84 % of the blocks of config 3's
 // row pairs held a run item and every block lived as long as its slowest wave (skipping the array x array items —
 // half of all items — shortened the kernel by 4 us out of 57).  One-wave blocks release each wave's table the
 // moment it ends.
-template <int SPW, int WPB>
+template <int WPB>
 __global__ void __launch_bounds__(64 * WPB) k_icount2(const Slot* __restrict__ slotsA, const uint8_t* __restrict__ arenaA,
                                                      const uint32_t* __restrict__ rowsA, const Slot* __restrict__ slotsB,
                                                      const uint8_t* __restrict__ arenaB, const uint32_t* __restrict__ rowsB, uint64_t n_pairs,
@@ -807,32 +794,24 @@ __global__ void __launch_bounds__(64 * WPB) k_icount2(const Slot* __restrict__ s
   sparse_paths &= 0xFFu;  // the ablation / cycle-stamp bits (8..23) exist in experiment builds only: every branch on them below folds away
 #endif
   const u64 t0 = ((sparse_paths >> 16) & 7u) ? __builtin_readcyclecounter() : 0;
-  constexpr int kWavesPerPair = kSlots / SPW;
+  constexpr int kWavesPerPair = kSlots;
   const int lane = threadIdx.x & 63;
   const int wv = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, and the compiler knows it
   const uint64_t wid = (uint64_t)blockIdx.x * WPB + (uint64_t)wv;
   const uint64_t pair = wid / kWavesPerPair;
   if (pair >= n_pairs) return;
-  const uint32_t slot0 = (uint32_t)(wid % kWavesPerPair) * SPW;
-  Slot sa[SPW], sb[SPW];
+  const uint32_t slot = (uint32_t)(wid % kWavesPerPair);
+  Slot sa, sb;
   if (items) {
     // the plan's resolved item records (k_resolve_items): {A's descriptor, B's descriptor} per (pair, slot), in item
     // order — ONE scalar round trip instead of row index -> descriptor, and neighbouring waves share its lines
-    const Slot* it = items + (pair * kSlots + slot0) * 2;
-#pragma unroll
-    for (int k = 0; k < SPW; ++k) {
-      sa[k] = it[2 * k];
-      sb[k] = it[2 * k + 1];
-    }
+    const Slot* it = items + (pair * kSlots + slot) * 2;
+    sa = it[0];
+    sb = it[1];
   } else {
     const uint32_t ra = rowsA[pair], rb = rowsB[pair];  // both row indexes in flight together
-    const Slot* da = slotsA + (uint64_t)ra * kSlots + slot0;
-    const Slot* db = slotsB + (uint64_t)rb * kSlots + slot0;
-#pragma unroll
-    for (int k = 0; k < SPW; ++k) {
-      sa[k] = da[k];
-      sb[k] = db[k];
-    }
+    sa = slotsA[(uint64_t)ra * kSlots + slot];
+    sb = slotsB[(uint64_t)rb * kSlots + slot];
   }
   u64* table = lds[wv];
   uint32_t part = 0, spart = 0;
@@ -852,14 +831,14 @@ __global__ void __launch_bounds__(64 * WPB) k_icount2(const Slot* __restrict__ s
   // that the wave that takes this wave's slot a generation later finds them in the L2 / Infinity Cache: 162.5 / 171.4 / 174.1 us
   // against 156.5-156.7, profiles/r06_pairs_prefetch_ahead_ab.txt.  More bytes in flight make this access pattern SLOWER.)
   if (!(sparse_paths & 0x400u)) {  // (0x400: timing experiment, descriptors only)
-    item_prefetch(sa[0], arenaA, sb[0], arenaB, lane, va, vb, sparse_paths);
+    item_prefetch(sa, arenaA, sb, arenaB, lane, va, vb, sparse_paths);
     if (stamp) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       t_mark = __builtin_readcyclecounter();
       if (stamp == 2) spart = (uint32_t)(t_mark - t_prev);
       if (stamp != 4) t_prev = t_mark;
     }
-    icount_items<0, SPW>(sa, arenaA, sb, arenaB, lane, table, mini[wv], va, vb, sparse_paths, part, spart);
+    icount_item(sa, arenaA, sb, arenaB, lane, table, mini[wv], va, vb, sparse_paths, part, spart);
     if (stamp >= 3) {
       const uint32_t keep = wave_reduce_add(part);  // (the decode has to finish before the stamp)
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -870,7 +849,7 @@ __global__ void __launch_bounds__(64 * WPB) k_icount2(const Slot* __restrict__ s
       part = 0;
     }
   } else {
-    spart = slot_n(sa[0]) + slot_n(sb[SPW - 1]);
+    spart = slot_n(sa) + slot_n(sb);
   }
   if (sparse_paths & 0x100u) return;  // (timing experiment: no output)
   const uint32_t c = wave_reduce_add(part) + spart;
@@ -889,11 +868,8 @@ __global__ void __launch_bounds__(64 * WPB) k_icount2(const Slot* __restrict__ s
 // worth 0-3 % on config 3's row pairs (those items are half of the waves and a seventh of the time; profiles/r04_pairs_lean_ab.json):
 // removed in round 5 with its option.)
 
-// out[pair] = the sum of the pair's waves' counts (per = 16 / SPW of them, consecutive)
-// (reset: a word this launch puts back to zero — k_icount3's chunk counter — or null)
-__global__ void __launch_bounds__(256) k_sum_wave_counts(const uint32_t* __restrict__ wave_counts, uint32_t per, uint64_t n_pairs, u64* __restrict__ out,
-                                                        uint32_t* __restrict__ reset) {
-  if (reset && blockIdx.x == 0 && threadIdx.x == 0) *reset = 0u;
+// out[pair] = the sum of the pair's waves' counts (`per` of them, consecutive)
+__global__ void __launch_bounds__(256) k_sum_wave_counts(const uint32_t* __restrict__ wave_counts, uint32_t per, uint64_t n_pairs, u64* __restrict__ out) {
   const uint64_t pair = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (pair >= n_pairs) return;
   const uint32_t* w = wave_counts + pair * per;

@@ -34,10 +34,8 @@ int32_t wire_upload(fbk_ctx* ctx, const uint8_t* blob, uint64_t len, const std::
   std::vector<fbk::WireDesc> descs(cs.size());
   uint64_t off = 0, row = 0;
   bool dense = n_slots > 0 && cs.size() == n_slots;
-  b->ring_regular = true;
   for (size_t i = 0; i < cs.size(); ++i) {
     const WireContainer& c = cs[i];
-    if (!ring_fits(c.type, c.len)) b->ring_regular = false;
     while (row < row_ids.size() && row_ids[row] != (c.key >> 4)) ++row;
     if (row == row_ids.size()) {
       delete b;

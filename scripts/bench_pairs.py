@@ -32,7 +32,7 @@ def main():
     ap.add_argument("--opt", action="append", default=[])
     ap.add_argument("--no-check", action="store_true", help="timing experiments on library builds that skip work: no comparison with the oracle")
     args = ap.parse_args()
-    if "pair_ablate" in args.variants or "pair_stamp" in args.variants or "pair_spw" in args.variants or any("ablate" in o or "stamp" in o for o in args.opt):
+    if "pair_ablate" in args.variants or "pair_stamp" in args.variants or any("ablate" in o or "stamp" in o for o in args.opt):
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         import _experiments
 

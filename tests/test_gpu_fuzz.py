@@ -19,13 +19,13 @@ def pair_kernel_generation(request, gpu_ctx):
     """Every test of this file runs with the round-2 pair kernels (k_icount / k_setop), with the round-3 ones (k_icount2 /
     k_setop2: table + probe, interior-map run decode, one-wave blocks) and with the library's own choice by payload size:
     each generation is checked against the oracle on every input of the file, not only on the rows the dispatch would
-    hand it."""
-    try:
+    hand it.  Value 3 was the removed k_icount3: the library must reject it in every build, and the test then runs on the
+    library's own choice."""
+    if request.param == 3:
+        with pytest.raises(L.FbkError):
+            gpu_ctx.set_option("pair_kernels", 3)
+    else:
         gpu_ctx.set_option("pair_kernels", request.param)
-    except Exception:
-        if request.param != 3:
-            raise
-        pytest.skip("k_icount3 exists in -DFBK_EXPERIMENTS builds only")
     yield request.param
     gpu_ctx.set_option("pair_kernels", 0)
 

@@ -361,3 +361,67 @@ def test_detached_plan_output_belongs_to_the_caller(gpu_ctx, mixed):
     plan.free()
     d.free()
     batch.free()
+
+
+@pytest.fixture(scope="module")
+def small_rows():
+    """2 shards x 2 rows = 4 rows of each kind: dense words [4, 16, 1024], mixed rows from datagen.random_row, and the 4 x 4
+    tables of |a & b| of both (numpy popcounts; the oracle's intersectionCount for the mixed rows)."""
+    from oracle import pyoracle as O
+
+    dense = D.dense_rows(4, 0.3, 8200)
+    dtab = np.array([[int(np.bitwise_count(dense[i] & dense[j]).sum()) for j in range(4)] for i in range(4)], dtype=np.uint64)
+    rng = D.rng_for(8201)
+    mixed = [D.random_row(rng, r) for r in range(4)]
+    by_slot = [{k & 15: c for k, c in row.items()} for row in mixed]
+    mtab = np.array([[sum(O.intersection_count(a[s], b[s]) for s in a if s in b) for b in by_slot] for a in by_slot], dtype=np.uint64)
+    dense.setflags(write=False)
+    return dense, dtab, mixed, mtab
+
+
+def test_caller_owned_counts_outlive_the_plan(gpu_ctx, small_rows):
+    """A plan created with device_counts_ptr writes the caller's buffer and never frees it: the counts are still there after the
+    plan is gone and the pool has handed the plan's own blocks out again, to eight further plans of the same shape."""
+    import torch
+
+    _, _, mixed, mtab = small_rows
+    M = gpu_ctx.upload([D.to_fbk_row(r) for r in mixed])
+    ra, rb = np.array([0, 1]), np.array([2, 3])
+    want = mtab[ra, rb]
+    try:
+        counts = torch.full((2,), -1, dtype=torch.int64, device="cuda:0")
+        torch.cuda.synchronize()
+        plan = gpu_ctx.plan(M, ra, M, rb, device_counts_ptr=counts.data_ptr())
+        plan.intersection_count()
+        gpu_ctx.synchronize()
+        plan.free()
+        for k in range(8):
+            p = gpu_ctx.plan(M, rb, M, ra[::-1].copy())  # library-owned counts, other values
+            p.intersection_count()
+            assert (p.read() == mtab[rb, ra[::-1]]).all(), k
+            p.free()
+        assert (counts.cpu().numpy().view(np.uint64) == want).all()
+    finally:
+        M.free()
+
+
+def test_freeing_the_hot_plan(gpu_ctx, small_rows):
+    """A dense plan counted twice is the context's hot plan (the second launch is k_icount_dense_resident); freeing it must leave
+    nothing behind that a later plan — maybe at the same address — could be mistaken for: its first count is cold, its next two
+    hot, all three right.  (This guards the sequence, not the compare-exchange in ~fbk_plan by itself: fbk_plan_free is not a
+    quiet call, so entering it has already ended the plan's residency when the destructor runs.)"""
+    dense, dtab, _, _ = small_rows
+    A = gpu_ctx.upload_dense(dense)
+    try:
+        plan = gpu_ctx.plan(A, [0, 1], A, [1, 0])
+        for _ in range(2):
+            plan.intersection_count()
+            assert (plan.read() == dtab[[0, 1], [1, 0]]).all()
+        plan.free()
+        plan = gpu_ctx.plan(A, [2, 3], A, [3, 3])
+        for k in range(3):
+            plan.intersection_count()
+            assert (plan.read() == dtab[[2, 3], [3, 3]]).all(), k
+        plan.free()
+    finally:
+        A.free()
