@@ -16,7 +16,11 @@ The rest of the entry points are fuzzed in
   tests/test_fuzz_prepared_cpu.py  the generator, the model against the oracle, and the coverage of the default iterations (no GPU)
   tests/test_gpu_fuzz_wire.py  the serialised uploads (roaring images, the ops-log replay, RBF files): valid images and mutants of them
   tests/wire_fuzz_gen.py       its case generator: images with their bit sets, tagged mutants, the oracle's verdict (no GPU)
-  tests/test_wire_fuzz_cpu.py  the host parsers over the same corpus under the sanitizers, and the coverage of the default iterations (no GPU)"""
+  tests/test_wire_fuzz_cpu.py  the host parsers over the same corpus under the sanitizers, and the coverage of the default iterations (no GPU)
+  tests/test_gpu_fuzz_topn.py  TopN, TopK, their prepared, partial and group forms and TopK-BSI on fields of 255 .. 2^20 rows: the candidate
+                               pass beyond one block stride and one index bin, the host / device ordering switch, planes beyond slot 0
+  tests/fuzz_topn_gen.py       its case generator: a pool of rows indexed many times, the expectations from the TopN model (no GPU)
+  tests/test_fuzz_topn_cpu.py  the generator, the regimes of the default iterations, and that its cases tell wrong candidate rules apart (no GPU)"""
 import os
 
 import numpy as np
