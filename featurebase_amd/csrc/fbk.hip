@@ -30,6 +30,7 @@
 #include "fbk_matrix_fused.hip.h"
 #include "fbk_matrix_fusedq.hip.h"
 #include "fbk_matrix_sum.hip.h"
+#include "fbk_matrix_cube.hip.h"
 #include "fbk_matrix_distinct.hip.h"
 #include "fbk_extract.hip.h"
 #include "fbk_sort.hip.h"
@@ -1389,6 +1390,7 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_dense_operands.inc"
 #include "fbk_query_api.inc"
 #include "fbk_matrix_sum_api.inc"
+#include "fbk_count_cube_api.inc"
 #include "fbk_matrix_distinct_api.inc"
 #include "fbk_extract_api.inc"
 #include "fbk_sort_api.inc"

@@ -125,6 +125,7 @@ SIGNATURES = {
     "fbk_fold_n_intersection_count": (C.c_int32, [_vp, C.c_int32, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
     "fbk_count_matrix": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "fbk_bsi_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "fbk_count_cube": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
     "fbk_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "fbk_query_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_count_matrix_distinct": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),

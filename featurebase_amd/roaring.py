@@ -757,6 +757,23 @@ class Context:
         del keep
         return vals, cnts, int(total.value)
 
+    # -- GroupBy over three fields -------------------------------------------------------------
+    def count_cube(self, p: Batch, rows_p, a: Batch, rows_a, b: Batch, rows_b, filt: Optional[Batch] = None, rows_f=None) -> np.ndarray:
+        """GroupBy(Rows(p), Rows(a), Rows(b)) in one pass (fbk_count_cube): for every triple the count of P_p ∩ A_i ∩ B_j ∩ filt,
+        summed over the shards.  rows_p [n_shards, n_p], rows_a [n_shards, n_a], rows_b [n_shards, n_b], rows_f [n_shards].
+        Returns uint64 [n_p, n_a, n_b]; a zero is a group the reference skips."""
+        rp = np.ascontiguousarray(rows_p, dtype=np.uint32)
+        n_shards, n_p = rp.shape
+        ra, rb = np.ascontiguousarray(rows_a, dtype=np.uint32), np.ascontiguousarray(rows_b, dtype=np.uint32)
+        assert ra.ndim == 2 and rb.ndim == 2 and ra.shape[0] == n_shards and rb.shape[0] == n_shards
+        n_a, n_b = ra.shape[1], rb.shape[1]
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        assert rf is None or rf.size == n_shards
+        out = np.zeros((n_p, n_a, n_b), dtype=np.uint64)
+        L.check(self.lib.fbk_count_cube(self.h, p.h, rp.ctypes.data, n_p, a.h, ra.ctypes.data, n_a, b.h, rb.ctypes.data, n_b,
+                                        filt.h if filt is not None else None, rf.ctypes.data if rf is not None else None, n_shards, out.ctypes.data))
+        return out
+
     # -- GroupBy with aggregate=Sum ------------------------------------------------------------
     def _msum_args(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, filt: Optional[Batch], rows_f):
         ra = np.ascontiguousarray(rows_a, dtype=np.uint32)

@@ -519,6 +519,29 @@ int32_t fbk_count_matrix(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_
                          const uint32_t* rows_f, uint32_t n_shards, uint64_t* out_total,
                          uint64_t* out_per_shard);
 
+/* ---- GroupBy over three fields ------------------------------------------------------------------
+ * out_total[(p*n_a + i)*n_b + j] = Σ_s |P.rows_p[s*n_p+p] ∩ A.rows_a[s*n_a+i] ∩ B.rows_b[s*n_b+j] ∩ F.rows_f[s]|
+ * for all groups at once: groupByIterator.Next's three levels (rows[0] ∩= filter, rows[1] ∩= rows[0], Count =
+ * rows[2].intersectionCount(rows[1]): executor.go:8829-8835, 8861-8867, 8893), the per-shard counts summed as mergeGroupCounts
+ * does (:3728).  A zero is a group the reference skips (:8913).  No intersection is materialised and the call synchronises once.
+ *  - Row lists [n_shards][n_p], [n_shards][n_a], [n_shards][n_b], [n_shards].  filter == NULL: no filter.  p, a and b may be
+ *    the same batch, and their row lists may be the same.
+ *  - n_p, n_a, n_b <= 4096 and n_p * n_a * n_b <= 2^24 (a 128 MiB result); beyond that FBK_E_INVALID, and the message says
+ *    to block the leading field.  NULL arguments and row indexes beyond a batch are FBK_E_INVALID, checked before any launch.
+ *    Every error leaves the context usable.
+ *  - n_shards == 0 writes a complete all-zero cube; n_p * n_a * n_b == 0 has nothing to write; both return FBK_OK.
+ *  - Counts come from the rows' WORDS, never from stored cardinalities.  Every element of out_total is written.  The result is
+ *    exact and does not depend on the grid, the chunking or the order of the adds (integer adds of per-shard counts < 2^21).
+ *  - One matrix-core pass per shard over dense rows, the partial cube of every shard of a chunk kept in scratch and summed on the
+ *    device; rows of batches that are not dense are densified first, a chunk of shards at a time:
+ *    most = max(1, min(n_shards, 2^30 / per_shard)) with per_shard = 8 * n_p * n_a * n_b + 2^17 * (the rows densified per shard:
+ *    n_p if P is not dense, n_a if A is not, n_b if B is not, 1 if the filter is not);
+ *    chunk = ceil(n_shards / ceil(n_shards / most)), the shards dealt evenly over the fewest chunks.  Device scratch is bounded by
+ *    that budget plus the result. */
+int32_t fbk_count_cube(fbk_ctx* ctx, const fbk_batch* p, const uint32_t* rows_p, uint32_t n_p, const fbk_batch* a,
+                       const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b, const uint32_t* rows_b, uint32_t n_b,
+                       const fbk_batch* filter, const uint32_t* rows_f, uint32_t n_shards, uint64_t* out_total);
+
 /* ---- GroupBy with aggregate=Sum(field=v) ------------------------------------------------------
  * For every pair (i, j), summed over the shards given (X = A.rows_a[s*n_a+i] ∩ B.rows_b[s*n_b+j] ∩ F.rows_f[s] ∩ exists):
  *   out_counts[i*n_b+j] = Σ_s |X|

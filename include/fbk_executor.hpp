@@ -1039,6 +1039,7 @@ class Executor {
   // rows (the call's limit per side; fbk_count / fbk_count_matrix take up to 2^22 rows against one).  counts[i * nb + j] =
   // columns WITH a value (the group's Count), sums + count * Base = its Agg (executeSumCountShard per group, executor.go:2155-2216).
   static constexpr size_t kSumBlock = 4096;
+  static constexpr size_t kCubeCells = size_t(1) << 24;  // groups per fbk_count_cube call
   // the rows [k0, k0 + bk) of every shard of a [n][nk] row list
   static std::vector<uint32_t> row_block(const std::vector<uint32_t>& rows, size_t n, size_t nk, size_t k0, size_t bk) {
     if (k0 == 0 && bk == nk) return rows;
@@ -1098,8 +1099,8 @@ class Executor {
           for (size_t j = 0; j < bj; ++j) distinct[(i0 + i) * nb + j0 + j] = int64_t(d[i * bj + j]);
       }
   }
-  // fields[level..]: the last two levels are one count-matrix call (one count-matrix-sum call with an aggregate); earlier levels
-  // materialise prefix ∩ row (gbi.rows[i].row.Intersect(gbi.rows[i-1].row), executor.go:8829-8834)
+  // fields[level..]: the last three levels are one count-cube call; with an aggregate the last two are one count-matrix-sum /
+  // -distinct call; earlier levels materialise prefix ∩ row (gbi.rows[i].row.Intersect(gbi.rows[i-1].row), executor.go:8829-8834)
   bool group_by_rec(const std::vector<std::string>& fields, size_t level, const RowSet* prefix, const GroupAgg& ag, uint64_t limit,
                     std::vector<FieldRow>& group, std::vector<GroupCount>& out) {
     const std::string& agg_field = ag.sum_field;
@@ -1170,7 +1171,49 @@ class Executor {
         }
       return true;
     }
-    for (size_t i = 0; i < na; ++i) {  // three or more fields left: fix this field's row
+    if (remaining == 3 && agg_field.empty() && ag.distinct_field.empty()) {
+      // plain counts of the last three levels: fbk_count_cube, the prefix row (if any) as the filter — no prefix ∩ row is
+      // materialised.  The leading field in blocks of bp rows (bp x kSumBlock x kSumBlock groups at most: the call's 2^24), the
+      // other two in blocks of kSumBlock rows; the groups of a block of leading rows are emitted before the next block is
+      // counted, so a small limit ends after the first one.
+      const Index::SetField& fb = idx_.sets_.at(fields[level + 1]);
+      const Index::SetField& fc = idx_.sets_.at(fields[level + 2]);
+      const size_t nb = fb.row_ids.size(), nc = fc.row_ids.size();
+      if (nb == 0 || nc == 0) return true;
+      const std::vector<uint32_t> rows_b = field_rows(fb), rows_c = field_rows(fc);
+      const size_t bp = std::max<size_t>(1, std::min(na, kCubeCells / (std::min(nb, kSumBlock) * std::min(nc, kSumBlock))));
+      std::vector<uint64_t> tot, c;
+      for (size_t p0 = 0; p0 < na; p0 += bp) {
+        const size_t np = std::min(bp, na - p0);
+        const std::vector<uint32_t> rp = row_block(rows_a, n, na, p0, np);
+        tot.assign(np * nb * nc, 0);
+        for (size_t i0 = 0; i0 < nb; i0 += kSumBlock)
+          for (size_t j0 = 0; j0 < nc; j0 += kSumBlock) {
+            const size_t bi = std::min(kSumBlock, nb - i0), bj = std::min(kSumBlock, nc - j0);
+            const std::vector<uint32_t> rb = row_block(rows_b, n, nb, i0, bi), rc = row_block(rows_c, n, nc, j0, bj);
+            c.assign(np * bi * bj, 0);
+            check(fbk_count_cube(idx_.ctx_, fa.batch, rp.data(), uint32_t(np), fb.batch, rb.data(), uint32_t(bi), fc.batch, rc.data(), uint32_t(bj),
+                                 prefix ? prefix->batch() : nullptr, prefix ? prefix->rows().data() : nullptr, uint32_t(n), c.data()));
+            for (size_t p = 0; p < np; ++p)
+              for (size_t i = 0; i < bi; ++i)
+                std::copy(c.begin() + (p * bi + i) * bj, c.begin() + (p * bi + i + 1) * bj, tot.begin() + (p * nb + i0 + i) * nc + j0);
+          }
+        for (size_t p = 0; p < np; ++p)
+          for (size_t i = 0; i < nb; ++i)
+            for (size_t j = 0; j < nc; ++j) {
+              const uint64_t cnt = tot[(p * nb + i) * nc + j];
+              if (!cnt) continue;
+              group.push_back({fields[level], fa.row_ids[p0 + p]});
+              group.push_back({fields[level + 1], fb.row_ids[i]});
+              group.push_back({fields[level + 2], fc.row_ids[j]});
+              const bool go = emit(group, cnt, 0, limit, out);
+              group.resize(group.size() - 3);
+              if (!go) return false;
+            }
+      }
+      return true;
+    }
+    for (size_t i = 0; i < na; ++i) {  // four or more fields left (three with an aggregate): fix this field's row
       RowSet r = leaf_row(fields[level], fa.row_ids[i]);
       group.push_back({fields[level], fa.row_ids[i]});
       bool go;

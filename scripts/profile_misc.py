@@ -8,7 +8,7 @@ Kernels reached: k_setop<OP> (generic pairs), k_encode_plan / k_scan_blocks / k_
 k_encode_write (optimize), k_count_range, k_fold_n<AND>, k_fold_scatter<XOR/ANDNOT>, k_shift, k_flip,
 k_bsi_add, k_bsi_values (+ hipcub sort), k_bsi_minmax_slot, k_bsi_range_slot / k_bsi_sum_slot, k_rows_flags, k_wire_copy (roaring
 upload + download), k_validate_recount, k_recount, k_rows_vs_filter + k_topn_filter,
-k_counts_to_bsi / k_cell_stats, k_count_matrix_fusedq, k_count_matrix<4>."""
+k_counts_to_bsi / k_cell_stats, k_count_matrix_fusedq, k_count_matrix<4>, k_cube_mfma."""
 import json
 import os
 import sys
@@ -69,6 +69,8 @@ rec("fbk_count_matrix 32 x 32 + filter, in-kernel decode (k_fused_program + k_co
 ctx.set_option("matrix_fused", 0)
 rec("fbk_count_matrix 8 x 8 + filter, generic pair kernel (k_count_matrix<4>)", nbytes * 17 / 65, lambda: ctx.count_matrix(batch, groups[:, :8], batch, groups[:, 32:40], F, fidx))
 ctx.set_option("matrix_fused", -1)
+rec("fbk_count_cube 8 x 32 x 32 + filter over densified rows (k_densify_rows + k_cube_mfma<8, true> + k_reduce_shards)", nbytes,
+    lambda: ctx.count_cube(batch, groups[:, :8], batch, groups[:, :32], batch, groups[:, 32:], F, fidx))
 # serialised roaring: download the union result and upload it again
 u, _ = ctx.union_n(batch, groups, L.SETOP_OPTIMIZE)
 blob = u.to_roaring()
