@@ -36,6 +36,7 @@
 #include "fbk_sort.hip.h"
 #include "fbk_quantile.hip.h"
 #include "fbk_distinct_rows.hip.h"
+#include "fbk_expr.hip.h"
 #include "fbk_wire_kernels.hip.h"
 
 using fbk::Slot;
@@ -1396,6 +1397,7 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_sort_api.inc"
 #include "fbk_quantile_api.inc"
 #include "fbk_distinct_rows_api.inc"
+#include "fbk_expr_api.inc"
 #include "fbk_prepared_api.inc"
 #include "fbk_wire_parse.h"
 #include "fbk_wire_api.inc"

@@ -12,6 +12,7 @@
 // latency-bound, 1.5 wavefronts per SIMD.
 #pragma once
 #include "fbk_kernels.hip.h"
+#include "fbk_bsi_prog.h"
 
 namespace fbk {
 
@@ -209,20 +210,7 @@ __global__ void __launch_bounds__(64) k_bsi_sum_slot(const Slot* __restrict__ sl
 // same program on its own containers, each bit plane read at most once per pass.  The loads
 // of U consecutive instructions are issued together (they do not depend on X/M/S), the
 // register updates are then applied in program order.
-enum BsiOp : uint32_t {
-  kLoadX = 0,   // X = row[r]
-  kAndX = 1,    // X &= row[r]            (Row.Intersect)
-  kAndnX = 2,   // X &= ~row[r]           (Row.Difference)
-  kMorXA = 3,   // M |= X & row[r]        (matched = matched.Union(remaining.Intersect(row)))
-  kMorXAn = 4,  // M |= X & ~row[r]       (matched = matched.Union(remaining.Difference(row)))
-  kMZero = 5,   // M = 0                  (NewRow())
-  kXFromM = 6,  // X = M
-  kZeroX = 7,   // X = 0
-  kSaveX = 8,   // S = X
-  kOrXS = 9,    // X |= S
-  kAndnXS = 10, // X &= ~S
-  kNop = 255
-};
+// enum BsiOp: fbk_bsi_prog.h (shared with the host-side program generators)
 
 template <int NW>
 __device__ __forceinline__ void bsi_apply(uint32_t op, u64 (&X)[NW], u64 (&M)[NW], u64 (&S)[NW], const u64 (&T)[NW]) {

@@ -14,7 +14,7 @@
 // It is the unit one (query, node) call of mapperLocal (executor.go:6742) becomes when the same query runs again —
 // and what the multi-GPU reduce wants: the partial matrix stays on the device for the collective.
 
-enum FbkQueryKind : int32_t { kQCountMatrix = 1, kQFoldICount = 2, kQBsiSum = 3, kQBsiRangeSum = 4, kQBsiRange = 5, kQFold = 6, kQTopN = 7, kQCountMatrixSum = 8 };
+enum FbkQueryKind : int32_t { kQCountMatrix = 1, kQFoldICount = 2, kQBsiSum = 3, kQBsiRangeSum = 4, kQBsiRange = 5, kQFold = 6, kQTopN = 7, kQCountMatrixSum = 8, kQExpr = 9 };
 
 struct fbk_query {
   fbk_ctx* ctx = nullptr;
@@ -55,6 +55,8 @@ struct fbk_query {
   FxProgram fx;
   // GroupBy with aggregate=Sum (fbk_matrix_sum_api.inc): row lists, scratch and the result {sums, counts}
   std::unique_ptr<MsumPlan> msum;
+  // a whole call tree (fbk_expr_api.inc): row lists, leaf table and lowered program; out == nullptr: FBK_EXPR_COUNT_ONLY
+  std::unique_ptr<ExprProgram> expr;
 };
 
 namespace {
@@ -305,6 +307,40 @@ int32_t fbk_query_fold(fbk_ctx* ctx, int32_t op, const fbk_batch* batch, const u
   return query_finish_create(ctx, q, rc, out_query);
 } FBK_ABI_CATCH(ctx)
 
+// A whole bitmap call tree (fbk_expr_eval / fbk_expr_count) prepared: the row list of every leaf, the leaf table and the lowered
+// program are validated and uploaded once, the output batch (one row of 8 KiB cells per shard; none with FBK_EXPR_COUNT_ONLY)
+// and the per-shard counts belong to the query; a run is memset + ONE launch of k_expr_slot.
+int32_t fbk_query_expr(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog, uint32_t n_shards,
+                       uint32_t flags, fbk_query** out_query) try {
+  FBK_ENTER(ctx);
+  if (int32_t rc = expr_args_ok(ctx, leaves, n_leaves, prog, n_prog)) return rc;
+  if (!out_query) return fail(FBK_E_INVALID, "NULL argument");
+  *out_query = nullptr;
+  if (flags & ~(FBK_SETOP_OPTIMIZE | FBK_EXPR_COUNT_ONLY)) return fail(FBK_E_INVALID, "unknown flags");
+  if (n_shards > (1u << 26)) return fail(FBK_E_INVALID, "too many shards in one call");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+  fbk_query* q = new (std::nothrow) fbk_query();
+  if (!q) return fail(FBK_E_NOMEM, "host allocation failed");
+  q->ctx = ctx;
+  q->kind = kQExpr;
+  q->n = n_shards;
+  q->out_flags = flags;
+  q->result_bytes = uint64_t(n_shards) * 8;
+  q->expr.reset(new ExprProgram());
+  int32_t rc = expr_prepare(ctx, leaves, n_leaves, prog, n_prog, n_shards, *q->expr);
+  if (!rc && n_shards == 0) rc = fail(FBK_E_INVALID, "query: no shards");
+  if (!rc && !(flags & FBK_EXPR_COUNT_ONLY)) {
+    rc = alloc_cell_batch(ctx, n_shards, &q->out);
+    if (!rc) rc = expr_output_keys(leaves, *q->expr, q->out);
+  }
+  if (!rc) {
+    const hipError_t e = q->result.alloc(ctx, q->result_bytes);
+    if (e != hipSuccess) rc = fail(FBK_E_NOMEM, std::string("query: ") + hipGetErrorString(e));
+  }
+  return query_finish_create(ctx, q, rc, out_query);  // (synchronises: the upload reads the program's host image)
+} FBK_ABI_CATCH(ctx)
+
 // TopN / TopK (fragment.top's per-shard rules, executeTopN's sum over shards: fbk_topn) with nothing left to the host:
 // row lists resident, per-shard counts, totals, and the ORDERING (a stable descending radix sort of (count, index) pairs that
 // start in index order: count descending, row index ascending inside one count) on the device with its scratch sized at
@@ -442,6 +478,15 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
       slots_rewritten(q->out);
       break;
     }
+    case kQExpr: {
+      const bool rows = q->out != nullptr;
+      if (rows && (acc || device_out)) return fail(FBK_E_INVALID, "query: a row result cannot be accumulated or redirected (only the FBK_EXPR_COUNT_ONLY form)");
+      if (!acc) HIP_TRY(hipMemsetAsync(out, 0, q->n * 8, ctx->stream));
+      rc = expr_launch(ctx, *q->expr, rows ? q->out->d_arena : nullptr, rows ? q->out->d_slots : nullptr, nullptr, static_cast<u64*>(out),
+                       rows && (q->out_flags & FBK_SETOP_OPTIMIZE));
+      if (!rc && rows) slots_rewritten(q->out);
+      break;
+    }
     case kQTopN: {
       if (acc) return fail(FBK_E_INVALID, "query: TopN totals are ordered by the run, not accumulable");
       if (device_out) return fail(FBK_E_INVALID, "query: a TopN writes its own buffers (fbk_query_read)");
@@ -506,6 +551,7 @@ int32_t fbk_query_read(fbk_ctx* ctx, fbk_query* q, void* out0, void* out1) try {
     case kQFoldICount:
     case kQBsiRange:  // out0 = the per-shard cardinalities of the result rows
     case kQFold:      // out0 = the per-group cardinalities
+    case kQExpr:      // out0 = the per-shard cardinalities of the tree's result
       if (out0) HIP_TRY(back.add(out0, q->last_out, q->result_bytes));
       HIP_TRY(back.finish());
       return FBK_OK;

@@ -70,6 +70,26 @@ class TopnArgs(C.Structure):
     _fields_ = [("a", C.c_void_p), ("rows_a", C.c_void_p), ("filter", C.c_void_p), ("rows_f", C.c_void_p), ("n_shards", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class ExprLeaf(C.Structure):
+    """Mirror of fbk_expr_leaf (include/fbk.h): one leaf of a bitmap call tree."""
+
+    _fields_ = [
+        ("batch", C.c_void_p),
+        ("rows", C.c_void_p),
+        ("kind", C.c_uint32),
+        ("op", C.c_int32),
+        ("bit_depth", C.c_uint32),
+        ("pad", C.c_uint32),
+        ("lo", C.c_int64),
+        ("hi", C.c_int64),
+    ]
+
+
+EXPR_ROW, EXPR_BSI, EXPR_BETWEEN = 0, 1, 2
+EXPR_PUSH, EXPR_AND, EXPR_OR, EXPR_XOR, EXPR_ANDNOT = 0, 1, 2, 3, 4
+EXPR_MAX_LEAVES, EXPR_MAX_PROG, EXPR_MAX_DEPTH = 256, 1024, 8
+EXPR_COUNT_ONLY = 2
+
 REDUCE_HOST, REDUCE_PEER, REDUCE_RCCL = 0, 1, 2
 
 _vp, _u32p, _u64p, _i32p = C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
@@ -159,6 +179,9 @@ SIGNATURES = {
     "fbk_bsi_range_sum_plan": (C.c_int32, [C.c_int32, C.c_uint32, C.c_int64, _vp, _vp, _vp, _vp]),
     "fbk_bsi_range_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_int32, C.c_uint32, C.c_int64, _vp, _vp, _vp, _vp]),
     "fbk_bsi_range_between": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, C.c_uint32, _vpp, _vp]),
+    "fbk_expr_count": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "fbk_expr_eval": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vpp, _vp]),
+    "fbk_query_expr": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_query_count_matrix": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_query_fold_intersection_count": (C.c_int32, [_vp, C.c_int32, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vpp]),
     "fbk_query_bsi_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_int32, C.c_int64, _vp, _vp, _vpp]),

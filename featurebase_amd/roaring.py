@@ -313,6 +313,59 @@ class Extract:
         self.close()
 
 
+class ExprLeaf:
+    """One leaf of a bitmap call tree (fbk_expr_leaf): a row per shard of `batch`, or a BSI predicate over the shard's fragment."""
+
+    def __init__(self, batch: Optional["Batch"], rows, kind: int = L.EXPR_ROW, op: int = 0, bit_depth: int = 0, lo: int = 0, hi: int = 0):
+        self.batch, self.kind, self.op, self.bit_depth, self.lo, self.hi = batch, kind, op, bit_depth, lo, hi
+        self.rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+
+
+def row_leaf(batch: "Batch", rows) -> ExprLeaf:
+    """rows[s] = ordinal of shard s's row in batch"""
+    return ExprLeaf(batch, rows)
+
+
+def bsi_leaf(batch: "Batch", base_rows, op: int, bit_depth: int, predicate: int) -> ExprLeaf:
+    """Row(v op predicate): base_rows[s] = base row of shard s's BSI fragment (the row Context.bsi_range gives)"""
+    return ExprLeaf(batch, base_rows, L.EXPR_BSI, op, bit_depth, predicate, 0)
+
+
+def between_leaf(batch: "Batch", base_rows, bit_depth: int, lo: int, hi: int) -> ExprLeaf:
+    """Row(lo <= v <= hi) (the row Context.bsi_range_between gives)"""
+    return ExprLeaf(batch, base_rows, L.EXPR_BETWEEN, 0, bit_depth, lo, hi)
+
+
+_EXPR_OPS = {"and": L.EXPR_AND, "or": L.EXPR_OR, "xor": L.EXPR_XOR, "andnot": L.EXPR_ANDNOT, "not": L.EXPR_ANDNOT}
+
+
+def compile_expr(tree) -> Tuple[List[ExprLeaf], np.ndarray]:
+    """A nested tuple such as ("and", ("or", leaf, leaf), ("andnot", exists, leaf), bsi_leaf) -> (leaves, postfix program) for
+    Context.expr_count / expr_eval / query_expr.  An operator folds its operands left to right (("andnot", a, b, c) = a minus b minus c);
+    ("not", exists, x) is ("andnot", exists, x), the way executeNotShard evaluates Not(x).  A leaf used twice is listed once."""
+    leaves: List[ExprLeaf] = []
+    index: dict = {}
+    prog: List[int] = []
+
+    def walk(t) -> None:
+        if isinstance(t, ExprLeaf):
+            if id(t) not in index:
+                index[id(t)] = len(leaves)
+                leaves.append(t)
+            prog.append((L.EXPR_PUSH << 24) | index[id(t)])
+            return
+        name, args = t[0], t[1:]
+        if name not in _EXPR_OPS or not args or (name == "not" and len(args) != 2):
+            raise ValueError(f"compile_expr: bad node {name!r} with {len(args)} operands")
+        walk(args[0])
+        for a in args[1:]:
+            walk(a)
+            prog.append(_EXPR_OPS[name] << 24)
+
+    walk(tree)
+    return leaves, np.asarray(prog, dtype=np.uint32)
+
+
 class Context:
     """One GPU.  Fails loudly when libfbk.so is missing or no gfx950 device is visible."""
 
@@ -994,6 +1047,41 @@ class Context:
         h = C.c_void_p()
         L.check(self.lib.fbk_bsi_range_between(self.h, batch.h, base.ctypes.data, base.size, bit_depth, lo, hi, flags, C.byref(h), counts.ctypes.data))
         return Batch(self, h.value), counts
+
+    # -- a whole bitmap call tree in one launch (fbk_expr_*) ------------------------------------
+    def _expr_args(self, leaves: Sequence[ExprLeaf], prog, n_shards: Optional[int]):
+        n = len(leaves)
+        arr = (L.ExprLeaf * max(n, 1))()
+        for i, lf in enumerate(leaves):
+            arr[i].batch = lf.batch.h.value if lf.batch is not None else None
+            arr[i].rows = lf.rows.ctypes.data
+            arr[i].kind, arr[i].op, arr[i].bit_depth, arr[i].lo, arr[i].hi = lf.kind, lf.op, lf.bit_depth, lf.lo, lf.hi
+        pr = np.ascontiguousarray(prog, dtype=np.uint32).reshape(-1)
+        if n_shards is None:
+            n_shards = int(leaves[0].rows.size) if n else 0
+        return arr, n, pr, n_shards
+
+    def expr_count(self, leaves: Sequence[ExprLeaf], prog, n_shards: Optional[int] = None) -> np.ndarray:
+        """Per-shard cardinality of the call tree (leaves, postfix program: compile_expr), nothing materialised."""
+        arr, n, pr, n_shards = self._expr_args(leaves, prog, n_shards)
+        out = np.zeros(n_shards, dtype=np.uint64)
+        L.check(self.lib.fbk_expr_count(self.h, arr, n, pr.ctypes.data, pr.size, n_shards, out.ctypes.data))
+        return out
+
+    def expr_eval(self, leaves: Sequence[ExprLeaf], prog, flags: int = 0, n_shards: Optional[int] = None) -> Tuple[Batch, np.ndarray]:
+        """The call tree's result as one row per shard of a new batch, and its cardinalities."""
+        arr, n, pr, n_shards = self._expr_args(leaves, prog, n_shards)
+        out = np.zeros(n_shards, dtype=np.uint64)
+        h = C.c_void_p()
+        L.check(self.lib.fbk_expr_eval(self.h, arr, n, pr.ctypes.data, pr.size, n_shards, flags, C.byref(h), out.ctypes.data))
+        return Batch(self, h.value), out
+
+    def query_expr(self, leaves: Sequence[ExprLeaf], prog, flags: int = 0, count_only: bool = False, n_shards: Optional[int] = None) -> Query:
+        """The call tree as a launch-only query: read() = cardinalities, output() = the result rows (not with count_only)."""
+        arr, n, pr, n_shards = self._expr_args(leaves, prog, n_shards)
+        h = C.c_void_p()
+        L.check(self.lib.fbk_query_expr(self.h, arr, n, pr.ctypes.data, pr.size, n_shards, flags | (L.EXPR_COUNT_ONLY if count_only else 0), C.byref(h)))
+        return Query(self, h.value, "rows", (n_shards,))
 
     def plan(self, a: Batch, rows_a, b: Batch, rows_b, device_counts_ptr: int = 0) -> Plan:
         ra = np.ascontiguousarray(rows_a, dtype=np.uint32)

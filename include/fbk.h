@@ -59,7 +59,8 @@ extern "C" {
  *      one-process-per-GPU exchange issued by the library itself).  fbk_batch_compact refuses a batch of another context;
  *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
  *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free; fbk_bsi_sort;
- *      fbk_extract_open_columns; fbk_bsi_quantiles; fbk_bsi_percentile; fbk_bsi_distinct_rows.
+ *      fbk_extract_open_columns; fbk_bsi_quantiles; fbk_bsi_percentile; fbk_bsi_distinct_rows;
+ *      fbk_expr_count / fbk_expr_eval / fbk_query_expr.
  *   5 (round 5): + fbk_topn_partials, options topn_semantics, matrix_shadow_arena_x.  CHANGED: fbk_topn / fbk_query_topn /
  *      fbk_group_topn with 0 < n < n_a return the reference's two-pass answer by default (topn_semantics = 1; = 0 restores
  *      round 4's exact top n of fbk_topn; round 4's per-member candidate rule of fbk_group_topn is gone — it was neither);
@@ -941,6 +942,61 @@ int32_t fbk_bsi_between_sum_plan(uint32_t bit_depth, int64_t lo, int64_t hi, uin
 int32_t fbk_bsi_range_between(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows,
                               uint32_t n_shards, uint32_t bit_depth, int64_t lo, int64_t hi, uint32_t flags,
                               fbk_batch** out_batch, uint64_t* out_counts);
+
+/* ---- a whole bitmap call tree in one launch ------------------------------------------------------
+ * The filter of a query — Intersect(Union(Row(a=1), Row(a=2)), Not(Row(b=3)), Row(x > 5)), the tree that
+ * executeBitmapCallShard (executor.go:1782) evaluates by recursion — as a list of LEAVES and a POSTFIX PROGRAM over them.
+ * For each shard s the program is evaluated over that shard's row of every leaf, one wavefront per (shard, slot): the
+ * intermediate values stay on chip, every leaf container is read once in its encoded form, the result is counted or written
+ * once (k_expr_slot).
+ *   leaf     kind FBK_EXPR_ROW: rows[s] = ordinal of the shard's row in `batch` (op, bit_depth, lo, hi unused);
+ *            FBK_EXPR_BSI: rows[s] = base row of the shard's BSI fragment, the leaf is Row(v op lo) (fbk_bsi_range's row);
+ *            FBK_EXPR_BETWEEN: Row(lo <= v <= hi) (fbk_bsi_range_between's row).  Leaves may come from different batches,
+ *            a leaf may be pushed any number of times, an empty row is a leaf like any other.
+ *   program  word = opcode << 24 | leaf index.  FBK_EXPR_PUSH pushes the leaf; FBK_EXPR_AND / _OR / _XOR / _ANDNOT pop b, pop
+ *            a and push a op b (ANDNOT: a \ b).  Not(x) is written PUSH exists, <x>, ANDNOT (executeNotShard); Shift crosses
+ *            containers and stays a call of its own (fbk_shift), its result enters as a ROW leaf.
+ *   limits   FBK_EXPR_MAX_LEAVES leaves, FBK_EXPR_MAX_PROG words, FBK_EXPR_MAX_DEPTH values on the stack at once.  Anything
+ *            beyond a limit, a stack underflow, more or fewer than one value left at the end, a leaf index >= n_leaves, an
+ *            unknown opcode or leaf kind, bit_depth > 64, a NULL batch or n_prog == 0 is FBK_E_INVALID before anything is
+ *            launched.  n_shards == 0 is FBK_OK with an empty result (fbk_expr_count, fbk_expr_eval); fbk_query_expr refuses it
+ *            with FBK_E_INVALID, as fbk_query_fold and fbk_query_bsi_range refuse a query over nothing.
+ *   fbk_expr_count   out_counts[s] = the cardinality of the result in shard s
+ *   fbk_expr_eval    the result as row s of a new batch (the caller frees it); flags as fbk_fold_n: 0 = bitmap cells,
+ *                    FBK_SETOP_OPTIMIZE = Container.optimize() applied and the arena compacted.  out_counts may be NULL.
+ *                    Keys: row s carries the high key bits of the first pushed leaf's row, as a fold carries its first row's;
+ *                    a program that starts with a BSI leaf has the default keys (s * 16 + slot), as fbk_bsi_range has.
+ *   fbk_query_expr   the prepared form (contract of fbk_query_fold / fbk_query_bsi_range): row lists, leaf table and program
+ *                    uploaded once, run = memset + ONE launch, read: out0 = uint64 cardinalities [n_shards];
+ *                    fbk_query_output lends the row batch.  flags | FBK_EXPR_COUNT_ONLY: no row batch (fbk_query_output
+ *                    fails), and only then fbk_query_run accepts device_out and FBK_QUERY_ACCUMULATE. */
+#define FBK_EXPR_ROW 0u
+#define FBK_EXPR_BSI 1u
+#define FBK_EXPR_BETWEEN 2u
+#define FBK_EXPR_PUSH 0u
+#define FBK_EXPR_AND 1u
+#define FBK_EXPR_OR 2u
+#define FBK_EXPR_XOR 3u
+#define FBK_EXPR_ANDNOT 4u
+#define FBK_EXPR_MAX_LEAVES 256u
+#define FBK_EXPR_MAX_PROG 1024u
+#define FBK_EXPR_MAX_DEPTH 8u
+#define FBK_EXPR_COUNT_ONLY 2u
+typedef struct fbk_expr_leaf {
+  const fbk_batch* batch;
+  const uint32_t* rows; /* [n_shards] */
+  uint32_t kind;        /* FBK_EXPR_ROW / _BSI / _BETWEEN */
+  int32_t op;           /* FBK_BSI_* for FBK_EXPR_BSI */
+  uint32_t bit_depth;
+  uint32_t pad;
+  int64_t lo, hi;       /* FBK_EXPR_BSI: lo is the predicate */
+} fbk_expr_leaf;
+int32_t fbk_expr_count(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
+                       uint32_t n_shards, uint64_t* out_counts);
+int32_t fbk_expr_eval(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
+                      uint32_t n_shards, uint32_t flags, fbk_batch** out_batch, uint64_t* out_counts);
+int32_t fbk_query_expr(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
+                       uint32_t n_shards, uint32_t flags, fbk_query** out_query);
 
 
 /* fragment.rows(start, filters...) (fragment.go:2465-2486; executeRowsShard, executor.go:4077-4182): which of
