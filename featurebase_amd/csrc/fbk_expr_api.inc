@@ -1,5 +1,6 @@
-// fbk_expr_api.inc — host side of fbk_expr_count / fbk_expr_eval and the pieces fbk_query_expr shares with them (included by
-// fbk.hip before fbk_prepared_api.inc).  The planner is fbk_expr_plan.h (HIP-free), the kernel k_expr_slot (fbk_expr.hip.h).
+// fbk_expr_api.inc — host side of fbk_expr_count / fbk_expr_eval / fbk_expr_bsi_agg and the pieces fbk_query_expr and
+// fbk_query_expr_bsi share with them (included by fbk.hip before fbk_prepared_api.inc).  The planner is fbk_expr_plan.h (HIP-free),
+// the kernels k_expr_slot and k_expr_agg_slot (fbk_expr.hip.h).
 
 namespace {
 
@@ -15,6 +16,12 @@ struct ExprProgram {
   const fbk::ExprLeaf* d_leaves() const { return reinterpret_cast<const fbk::ExprLeaf*>(static_cast<const uint8_t*>(buf.p) + off_leaves); }
   const uint32_t* d_prog() const { return reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(buf.p) + off_prog); }
   uint32_t lds_bytes() const { return (1u + plan.slots) * 8192u; }
+  // fbk_expr_bsi_agg / fbk_query_expr_bsi: the BSI field the aggregate terminal scans (agg_batch == nullptr: none)
+  const fbk_batch* agg_batch = nullptr;
+  DevBuf agg_base;  // its base rows [n_shards]
+  uint32_t agg = 0, agg_depth = 0;
+  // words per shard the aggregate leaves on the device: {psum, nsum, count}, or 16 slots of {magnitude, count | scan flag}
+  uint64_t agg_words() const { return agg == FBK_AGG_SUM ? 3 : 2 * uint64_t(fbk::kSlots); }
 };
 
 int32_t expr_args_ok(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog) {
@@ -58,8 +65,8 @@ int32_t expr_prepare(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leave
   return FBK_OK;
 }
 
-// one launch: the tree over every (shard, slot).  outSlots == NULL: counts only.
-int32_t expr_launch(fbk_ctx* ctx, ExprProgram& P, uint8_t* arenaO, Slot* outSlots, uint32_t* outRuns, u64* d_counts, bool encode) {
+// a leaf's batch that was optimised / compacted since the upload: its pointers in the device's leaf table are renewed
+int32_t expr_patch_leaves(fbk_ctx* ctx, ExprProgram& P) {
   bool patched = false;
   for (size_t l = 0; l < P.batches.size(); ++l) {
     fbk::ExprLeaf& h = P.h_leaves[l];
@@ -69,10 +76,16 @@ int32_t expr_launch(fbk_ctx* ctx, ExprProgram& P, uint8_t* arenaO, Slot* outSlot
       patched = true;
     }
   }
-  if (patched) {  // (a leaf's batch was optimised / compacted since the upload)
+  if (patched) {
     HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(P.buf.p) + P.off_leaves, P.h_leaves.data(), P.h_leaves.size() * sizeof(fbk::ExprLeaf), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
   }
+  return FBK_OK;
+}
+
+// one launch: the tree over every (shard, slot).  outSlots == NULL: counts only.
+int32_t expr_launch(fbk_ctx* ctx, ExprProgram& P, uint8_t* arenaO, Slot* outSlots, uint32_t* outRuns, u64* d_counts, bool encode) {
+  if (int32_t rc = expr_patch_leaves(ctx, P)) return rc;
   {
     KernelSpan span(ctx);
     hipLaunchKernelGGL(fbk::k_expr_slot, dim3(uint32_t(uint64_t(P.n_shards) * fbk::kSlots)), dim3(64), P.lds_bytes(), ctx->stream, P.d_leaves(), P.d_prog(),
@@ -94,6 +107,61 @@ int32_t expr_output_keys(const fbk_expr_leaf* leaves, const ExprProgram& P, fbk_
     set_row_keys(o, s, high);
   }
   return FBK_OK;
+}
+
+// ---- the tree, then Sum / Min / Max of a BSI field over its result (k_expr_agg_slot) -------------------------------------------
+
+// what fbk_expr_bsi_agg and fbk_query_expr_bsi ask of the aggregate's own arguments (the tree's: expr_prepare); no device work
+int32_t expr_agg_args_ok(uint32_t agg, const fbk_batch* batch, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards) {
+  if (agg > FBK_AGG_MAX) return fail(FBK_E_INVALID, "expr: unknown aggregate (FBK_AGG_SUM, FBK_AGG_MIN, FBK_AGG_MAX)");
+  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (!batch || (n_shards && !base_rows)) return fail(FBK_E_INVALID, "NULL argument");
+  if (n_shards > (1u << 26)) return fail(FBK_E_INVALID, "too many shards in one call");
+  return bsi_rows_ok(base_rows, n_shards, bit_depth, batch->n_rows);
+}
+
+// expr_prepare plus the field: everything validated, the base rows uploaded.  Nothing is launched on a failure.
+int32_t expr_agg_prepare(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog, uint32_t n_shards,
+                         uint32_t agg, const fbk_batch* batch, const uint32_t* base_rows, uint32_t bit_depth, ExprProgram& P) {
+  if (int32_t rc = expr_prepare(ctx, leaves, n_leaves, prog, n_prog, n_shards, P)) return rc;
+  P.agg_batch = batch;
+  P.agg = agg;
+  P.agg_depth = bit_depth;
+  if (n_shards == 0) return FBK_OK;
+  if (int32_t rc = upload_rows(ctx, base_rows, n_shards, UINT32_MAX, P.agg_base)) return rc;  // (validated: expr_agg_args_ok)
+  if (P.lds_bytes() > 65536u)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(fbk::k_expr_agg_slot), hipFuncAttributeMaxDynamicSharedMemorySize, int(P.lds_bytes())));
+  return FBK_OK;
+}
+
+// one launch into d_out [n_shards * P.agg_words()].  Sum adds to what is there (the caller zeroes it, or accumulates); Min / Max
+// write every word.  The field's batch is read where it is NOW (a batch compacted since the prepare has new pointers).
+int32_t expr_agg_launch(fbk_ctx* ctx, ExprProgram& P, u64* d_out) {
+  if (int32_t rc = expr_patch_leaves(ctx, P)) return rc;
+  {
+    KernelSpan span(ctx);
+    hipLaunchKernelGGL(fbk::k_expr_agg_slot, dim3(uint32_t(uint64_t(P.n_shards) * fbk::kSlots)), dim3(64), P.lds_bytes(), ctx->stream, P.d_leaves(), P.d_prog(),
+                       uint32_t(P.plan.ins.size()), P.n_shards, P.plan.slots, P.agg_batch->d_slots, P.agg_batch->d_arena, P.agg_base.as<uint32_t>(),
+                       P.agg_depth, P.agg, d_out);
+  }
+  HIP_TRY(hipGetLastError());
+  return FBK_OK;
+}
+
+// the downloaded words -> per-shard (value, count), as fbk_bsi_sum / fbk_bsi_min / fbk_bsi_max give them; either output may be NULL
+void expr_agg_fold(const ExprProgram& P, const u64* h, int64_t* out_vals, uint64_t* out_counts) {
+  std::vector<int64_t> v(P.n_shards);
+  std::vector<uint64_t> c(P.n_shards);
+  if (P.agg == FBK_AGG_SUM) {
+    for (uint32_t s = 0; s < P.n_shards; ++s) {  // Total(): int64(psum) - int64(nsum) (roaring/filter.go:1106-1108)
+      v[s] = int64_t(h[s * 3 + 0] - h[s * 3 + 1]);
+      c[s] = h[s * 3 + 2];
+    }
+  } else {
+    bsi_minmax_fold(h, P.n_shards, P.agg == FBK_AGG_MAX ? 1u : 0u, v.data(), c.data());
+  }
+  if (out_vals) std::memcpy(out_vals, v.data(), uint64_t(P.n_shards) * 8);
+  if (out_counts) std::memcpy(out_counts, c.data(), uint64_t(P.n_shards) * 8);
 }
 
 }  // namespace
@@ -152,6 +220,33 @@ int32_t fbk_expr_eval(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leav
   }
   (void)hipStreamSynchronize(ctx->stream);
   *out_batch = out.release();
+  return FBK_OK;
+} FBK_ABI_CATCH(ctx)
+
+int32_t fbk_expr_bsi_agg(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog, uint32_t n_shards,
+                         uint32_t agg, const fbk_batch* batch, const uint32_t* base_rows, uint32_t bit_depth, int64_t* out_vals,
+                         uint64_t* out_counts) try {
+  FBK_ENTER(ctx);
+  if (int32_t rc = expr_args_ok(ctx, leaves, n_leaves, prog, n_prog)) return rc;
+  if (n_shards && (!out_vals || !out_counts)) return fail(FBK_E_INVALID, "NULL argument");
+  if (int32_t rc = expr_agg_args_ok(agg, batch, base_rows, bit_depth, n_shards)) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+  ExprProgram P;
+  DevBuf dout;
+  struct Drain {  // the upload reads P.blob: nothing of P may go while the stream still holds work
+    fbk_ctx* c;
+    ~Drain() { (void)hipStreamSynchronize(c->stream); }
+  } drain{ctx};
+  if (int32_t rc = expr_agg_prepare(ctx, leaves, n_leaves, prog, n_prog, n_shards, agg, batch, base_rows, bit_depth, P)) return rc;
+  if (n_shards == 0) return FBK_OK;
+  const uint64_t n_words = uint64_t(n_shards) * P.agg_words();
+  HIP_TRY(dout.alloc(ctx, n_words * 8));
+  if (agg == FBK_AGG_SUM) HIP_TRY(hipMemsetAsync(dout.p, 0, n_words * 8, ctx->stream));
+  if (int32_t rc = expr_agg_launch(ctx, P, dout.as<u64>())) return rc;
+  std::vector<u64> h;
+  if (int32_t rc = download_words(ctx, dout, n_words, h)) return rc;
+  expr_agg_fold(P, h.data(), out_vals, out_counts);
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 

@@ -14,7 +14,7 @@
 // It is the unit one (query, node) call of mapperLocal (executor.go:6742) becomes when the same query runs again —
 // and what the multi-GPU reduce wants: the partial matrix stays on the device for the collective.
 
-enum FbkQueryKind : int32_t { kQCountMatrix = 1, kQFoldICount = 2, kQBsiSum = 3, kQBsiRangeSum = 4, kQBsiRange = 5, kQFold = 6, kQTopN = 7, kQCountMatrixSum = 8, kQExpr = 9 };
+enum FbkQueryKind : int32_t { kQCountMatrix = 1, kQFoldICount = 2, kQBsiSum = 3, kQBsiRangeSum = 4, kQBsiRange = 5, kQFold = 6, kQTopN = 7, kQCountMatrixSum = 8, kQExpr = 9, kQExprBsi = 10 };
 
 struct fbk_query {
   fbk_ctx* ctx = nullptr;
@@ -55,7 +55,8 @@ struct fbk_query {
   FxProgram fx;
   // GroupBy with aggregate=Sum (fbk_matrix_sum_api.inc): row lists, scratch and the result {sums, counts}
   std::unique_ptr<MsumPlan> msum;
-  // a whole call tree (fbk_expr_api.inc): row lists, leaf table and lowered program; out == nullptr: FBK_EXPR_COUNT_ONLY
+  // a whole call tree (fbk_expr_api.inc): row lists, leaf table and lowered program; out == nullptr: FBK_EXPR_COUNT_ONLY.
+  // kQExprBsi: with the field of the aggregate terminal; `result` holds the raw words (ExprProgram::agg_words per shard)
   std::unique_ptr<ExprProgram> expr;
 };
 
@@ -341,6 +342,35 @@ int32_t fbk_query_expr(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_lea
   return query_finish_create(ctx, q, rc, out_query);  // (synchronises: the upload reads the program's host image)
 } FBK_ABI_CATCH(ctx)
 
+// Sum / Min / Max of a BSI field over a whole call tree (fbk_expr_bsi_agg) prepared: row lists, leaf table, program and the field's
+// base rows are validated and uploaded once; a run is memset + ONE launch of k_expr_agg_slot into the raw per-shard words.
+int32_t fbk_query_expr_bsi(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog, uint32_t n_shards,
+                           uint32_t agg, const fbk_batch* batch, const uint32_t* base_rows, uint32_t bit_depth, fbk_query** out_query) try {
+  FBK_ENTER(ctx);
+  if (int32_t rc = expr_args_ok(ctx, leaves, n_leaves, prog, n_prog)) return rc;
+  if (!out_query) return fail(FBK_E_INVALID, "NULL argument");
+  *out_query = nullptr;
+  if (int32_t rc = expr_agg_args_ok(agg, batch, base_rows, bit_depth, n_shards)) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int32_t rc = set_device(ctx)) return rc;
+  fbk_query* q = new (std::nothrow) fbk_query();
+  if (!q) return fail(FBK_E_NOMEM, "host allocation failed");
+  q->ctx = ctx;
+  q->kind = kQExprBsi;
+  q->a = batch;
+  q->depth = bit_depth;
+  q->n = n_shards;
+  q->expr.reset(new ExprProgram());
+  int32_t rc = expr_agg_prepare(ctx, leaves, n_leaves, prog, n_prog, n_shards, agg, batch, base_rows, bit_depth, *q->expr);
+  if (!rc && n_shards == 0) rc = fail(FBK_E_INVALID, "query: no shards");
+  if (!rc) {
+    q->result_bytes = uint64_t(n_shards) * q->expr->agg_words() * 8;
+    const hipError_t e = q->result.alloc(ctx, q->result_bytes);
+    if (e != hipSuccess) rc = fail(FBK_E_NOMEM, std::string("query: ") + hipGetErrorString(e));
+  }
+  return query_finish_create(ctx, q, rc, out_query);  // (synchronises: the upload reads the program's host image)
+} FBK_ABI_CATCH(ctx)
+
 // TopN / TopK (fragment.top's per-shard rules, executeTopN's sum over shards: fbk_topn) with nothing left to the host:
 // row lists resident, per-shard counts, totals, and the ORDERING (a stable descending radix sort of (count, index) pairs that
 // start in index order: count descending, row index ascending inside one count) on the device with its scratch sized at
@@ -487,6 +517,13 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
       if (!rc && rows) slots_rewritten(q->out);
       break;
     }
+    case kQExprBsi: {
+      const bool sum = q->expr->agg == FBK_AGG_SUM;  // {psum, nsum, count} add up; the slot records of Min / Max do not
+      if (!sum && (acc || device_out)) return fail(FBK_E_INVALID, "query: Min / Max write per-slot records of their own (fbk_query_read), nothing to accumulate or redirect");
+      if (sum && !acc) HIP_TRY(hipMemsetAsync(out, 0, q->result_bytes, ctx->stream));
+      rc = expr_agg_launch(ctx, *q->expr, static_cast<u64*>(out));
+      break;
+    }
     case kQTopN: {
       if (acc) return fail(FBK_E_INVALID, "query: TopN totals are ordered by the run, not accumulable");
       if (device_out) return fail(FBK_E_INVALID, "query: a TopN writes its own buffers (fbk_query_read)");
@@ -591,6 +628,13 @@ int32_t fbk_query_read(fbk_ctx* ctx, fbk_query* q, void* out0, void* out1) try {
           if (counts) counts[s] = h[s * 4 + 2] + h[s * 4 + 3];
         }
       }
+      return FBK_OK;
+    }
+    case kQExprBsi: {  // out0 = int64 values [n_shards], out1 = uint64 counts [n_shards]
+      std::vector<u64> h(q->n * q->expr->agg_words());
+      HIP_TRY(back.add(h.data(), q->last_out, h.size() * 8));
+      HIP_TRY(back.finish());
+      expr_agg_fold(*q->expr, h.data(), static_cast<int64_t*>(out0), static_cast<uint64_t*>(out1));
       return FBK_OK;
     }
     default:

@@ -1205,27 +1205,9 @@ int32_t fbk_bsi_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_r
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 
-// Min (mode 0) / Max (mode 1) per shard.  The caller holds ctx->mu, has set the device and checked the pointers; n_shards != 0.
-// Also fbk_bsi_distinct_rows' window when arithmetic does not bound it.
-static int32_t bsi_minmax_locked(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
-                                 uint32_t bit_depth, uint32_t mode, const fbk_batch* filter, const uint32_t* rows_f,
-                                 int64_t* out_vals, uint64_t* out_counts) {
-  BsiShardOperands ops;
-  if (int32_t rc = ops.upload(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f)) return rc;
-  // one wavefront per (shard, slot), folded per shard on the host: min over a shard = the smallest of
-  // its slots' minima, its count = the sum over the slots that reach it (max alike)
-  const uint64_t n_out = uint64_t(n_shards) * fbk::kSlots;
-  DevBuf d2;
-  HIP_TRY(d2.alloc(ctx, n_out * 16));
-  const FilterArgs f(filter, ops.filter_rows());
-  {
-    KernelSpan span(ctx);
-    hipLaunchKernelGGL(fbk::k_bsi_minmax_slot, dim3(uint32_t(n_out)), dim3(64), 0, ctx->stream, batch->d_slots, batch->d_arena,
-                       ops.base(), n_shards, bit_depth, mode, f.slots, f.arena, f.rows, d2.as<u64>());
-  }
-  HIP_TRY(hipGetLastError());
-  std::vector<u64> h2;
-  if (int32_t rc = download_words(ctx, d2, n_out * 2, h2)) return rc;
+// The host fold of k_bsi_minmax_slot's records (also k_expr_agg_slot's): h2[(s * 16 + slot) * 2] = {magnitude, count | scan flag}
+// -> Min (mode 0) / Max (mode 1) of shard s and the number of columns that hold it; (0, 0) where nothing qualifies.
+static void bsi_minmax_fold(const u64* h2, uint32_t n_shards, uint32_t mode, int64_t* out_vals, uint64_t* out_counts) {
   for (uint32_t s = 0; s < n_shards; ++s) {
     // fragment.min (fragment.go:754-779): negatives present => -(maxUnsigned over them), else
     // minUnsigned over everything considered; fragment.max (:803-830) with positives.  "present" is
@@ -1251,6 +1233,30 @@ static int32_t bsi_minmax_locked(fbk_ctx* ctx, const fbk_batch* batch, const uin
     out_vals[s] = cnt ? best : 0;
     out_counts[s] = cnt;
   }
+}
+
+// Min (mode 0) / Max (mode 1) per shard.  The caller holds ctx->mu, has set the device and checked the pointers; n_shards != 0.
+// Also fbk_bsi_distinct_rows' window when arithmetic does not bound it.
+static int32_t bsi_minmax_locked(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint32_t n_shards,
+                                 uint32_t bit_depth, uint32_t mode, const fbk_batch* filter, const uint32_t* rows_f,
+                                 int64_t* out_vals, uint64_t* out_counts) {
+  BsiShardOperands ops;
+  if (int32_t rc = ops.upload(ctx, batch, base_rows, n_shards, bit_depth, filter, rows_f)) return rc;
+  // one wavefront per (shard, slot), folded per shard on the host: min over a shard = the smallest of
+  // its slots' minima, its count = the sum over the slots that reach it (max alike)
+  const uint64_t n_out = uint64_t(n_shards) * fbk::kSlots;
+  DevBuf d2;
+  HIP_TRY(d2.alloc(ctx, n_out * 16));
+  const FilterArgs f(filter, ops.filter_rows());
+  {
+    KernelSpan span(ctx);
+    hipLaunchKernelGGL(fbk::k_bsi_minmax_slot, dim3(uint32_t(n_out)), dim3(64), 0, ctx->stream, batch->d_slots, batch->d_arena,
+                       ops.base(), n_shards, bit_depth, mode, f.slots, f.arena, f.rows, d2.as<u64>());
+  }
+  HIP_TRY(hipGetLastError());
+  std::vector<u64> h2;
+  if (int32_t rc = download_words(ctx, d2, n_out * 2, h2)) return rc;
+  bsi_minmax_fold(h2.data(), n_shards, mode, out_vals, out_counts);
   return FBK_OK;
 }
 

@@ -87,6 +87,7 @@ class ExprLeaf(C.Structure):
 
 EXPR_ROW, EXPR_BSI, EXPR_BETWEEN = 0, 1, 2
 EXPR_PUSH, EXPR_AND, EXPR_OR, EXPR_XOR, EXPR_ANDNOT = 0, 1, 2, 3, 4
+AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2
 EXPR_MAX_LEAVES, EXPR_MAX_PROG, EXPR_MAX_DEPTH = 256, 1024, 8
 EXPR_COUNT_ONLY = 2
 
@@ -182,6 +183,8 @@ SIGNATURES = {
     "fbk_expr_count": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp]),
     "fbk_expr_eval": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vpp, _vp]),
     "fbk_query_expr": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vpp]),
+    "fbk_expr_bsi_agg": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "fbk_query_expr_bsi": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vpp]),
     "fbk_query_count_matrix": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_query_fold_intersection_count": (C.c_int32, [_vp, C.c_int32, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vpp]),
     "fbk_query_bsi_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_int32, C.c_int64, _vp, _vp, _vpp]),

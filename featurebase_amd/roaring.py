@@ -1083,6 +1083,35 @@ class Context:
         L.check(self.lib.fbk_query_expr(self.h, arr, n, pr.ctypes.data, pr.size, n_shards, flags | (L.EXPR_COUNT_ONLY if count_only else 0), C.byref(h)))
         return Query(self, h.value, "rows", (n_shards,))
 
+    def expr_bsi_agg(self, agg: int, leaves: Sequence[ExprLeaf], prog, batch: Batch, base_rows, bit_depth: int, n_shards: Optional[int] = None):
+        """Sum / Min / Max (agg = L.AGG_*) of the int field (batch, base_rows, bit_depth) over the call tree's result, in the tree's
+        own launch: per shard (values int64, counts uint64), equal to bsi_sum / bsi_min / bsi_max with expr_eval's row as filter."""
+        arr, n, pr, n_shards = self._expr_args(leaves, prog, n_shards)
+        base = np.ascontiguousarray(base_rows, dtype=np.uint32)
+        vals, counts = np.zeros(n_shards, dtype=np.int64), np.zeros(n_shards, dtype=np.uint64)
+        L.check(self.lib.fbk_expr_bsi_agg(self.h, arr, n, pr.ctypes.data, pr.size, n_shards, agg, batch.h if batch is not None else None, base.ctypes.data,
+                                          bit_depth, vals.ctypes.data, counts.ctypes.data))
+        return vals, counts
+
+    def expr_bsi_sum(self, leaves: Sequence[ExprLeaf], prog, batch: Batch, base_rows, bit_depth: int, n_shards: Optional[int] = None):
+        return self.expr_bsi_agg(L.AGG_SUM, leaves, prog, batch, base_rows, bit_depth, n_shards)
+
+    def expr_bsi_min(self, leaves: Sequence[ExprLeaf], prog, batch: Batch, base_rows, bit_depth: int, n_shards: Optional[int] = None):
+        return self.expr_bsi_agg(L.AGG_MIN, leaves, prog, batch, base_rows, bit_depth, n_shards)
+
+    def expr_bsi_max(self, leaves: Sequence[ExprLeaf], prog, batch: Batch, base_rows, bit_depth: int, n_shards: Optional[int] = None):
+        return self.expr_bsi_agg(L.AGG_MAX, leaves, prog, batch, base_rows, bit_depth, n_shards)
+
+    def query_expr_bsi(self, agg: int, leaves: Sequence[ExprLeaf], prog, batch: Batch, base_rows, bit_depth: int, n_shards: Optional[int] = None) -> Query:
+        """expr_bsi_agg as a launch-only query: read() = (values, counts).  AGG_SUM runs may go to / accumulate into a caller's
+        device buffer of 24 bytes per shard ({psum, nsum, count})."""
+        arr, n, pr, n_shards = self._expr_args(leaves, prog, n_shards)
+        base = np.ascontiguousarray(base_rows, dtype=np.uint32)
+        h = C.c_void_p()
+        L.check(self.lib.fbk_query_expr_bsi(self.h, arr, n, pr.ctypes.data, pr.size, n_shards, agg, batch.h if batch is not None else None, base.ctypes.data,
+                                            bit_depth, C.byref(h)))
+        return Query(self, h.value, "bsi", (n_shards,))
+
     def plan(self, a: Batch, rows_a, b: Batch, rows_b, device_counts_ptr: int = 0) -> Plan:
         ra = np.ascontiguousarray(rows_a, dtype=np.uint32)
         rb = np.ascontiguousarray(rows_b, dtype=np.uint32)

@@ -60,7 +60,7 @@ extern "C" {
  *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
  *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free; fbk_bsi_sort;
  *      fbk_extract_open_columns; fbk_bsi_quantiles; fbk_bsi_percentile; fbk_bsi_distinct_rows;
- *      fbk_expr_count / fbk_expr_eval / fbk_query_expr.
+ *      fbk_expr_count / fbk_expr_eval / fbk_query_expr; fbk_expr_bsi_agg / fbk_query_expr_bsi.
  *   5 (round 5): + fbk_topn_partials, options topn_semantics, matrix_shadow_arena_x.  CHANGED: fbk_topn / fbk_query_topn /
  *      fbk_group_topn with 0 < n < n_a return the reference's two-pass answer by default (topn_semantics = 1; = 0 restores
  *      round 4's exact top n of fbk_topn; round 4's per-member candidate rule of fbk_group_topn is gone — it was neither);
@@ -997,6 +997,33 @@ int32_t fbk_expr_eval(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leav
                       uint32_t n_shards, uint32_t flags, fbk_batch** out_batch, uint64_t* out_counts);
 int32_t fbk_query_expr(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
                        uint32_t n_shards, uint32_t flags, fbk_query** out_query);
+
+/* Sum / Min / Max of an int field over a call tree, in the tree's own launch: SELECT SUM(x) ... WHERE <tree>.  The reference
+ * evaluates the filter (executeSum / executeMin / executeMax, executor.go -> executeBitmapCallShard) and hands the Row to
+ * fragment.sum / min / max (fragment.go:724-853); fbk_expr_eval followed by fbk_bsi_sum / _min / _max does the same with the
+ * row written out and read back.  Here the filter stays in the wavefront's registers and the field's planes stream past it
+ * (k_expr_agg_slot).  leaves / prog / n_shards and every tree error: as fbk_expr_count.  batch / base_rows /
+ * bit_depth: the BSI field as fbk_bsi_sum takes it (it may be a leaf's own batch).  agg: FBK_AGG_SUM, _MIN or _MAX.
+ *   out_vals[s], out_counts[s]   bit for bit what fbk_bsi_sum / fbk_bsi_min / fbk_bsi_max return for shard s with the tree's row
+ *                    as their filter: Base not added, Sum wraps in uint64, (0, 0) where nothing qualifies.
+ *   FBK_E_INVALID before anything is launched: a tree error, agg > 2, bit_depth > 64, a NULL batch, NULL base_rows or outputs
+ *                    with n_shards > 0, base_rows[s] + bit_depth + 2 > the batch's rows, n_shards > 2^26.  n_shards == 0 is
+ *                    FBK_OK; fbk_query_expr_bsi refuses it, as fbk_query_expr does.
+ *   fbk_query_expr_bsi   the prepared form (contract of fbk_query_bsi_sum): everything uploaded once, run = memset + ONE launch,
+ *                    read: out0 = int64 values [n_shards], out1 = uint64 counts [n_shards]; a leaf batch or the field batch
+ *                    compacted since is picked up by the next run.  FBK_AGG_SUM leaves {psum, nsum, count} per shard (24 bytes,
+ *                    uint64, all three additive with wrap-around): fbk_query_run accepts device_out, and FBK_QUERY_ACCUMULATE adds
+ *                    a run to what the buffer holds.  _MIN / _MAX leave per-slot records only fbk_query_read folds: device_out
+ *                    must be NULL and FBK_QUERY_ACCUMULATE is FBK_E_INVALID. */
+#define FBK_AGG_SUM 0u
+#define FBK_AGG_MIN 1u
+#define FBK_AGG_MAX 2u
+int32_t fbk_expr_bsi_agg(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
+                         uint32_t n_shards, uint32_t agg, const fbk_batch* batch, const uint32_t* base_rows, uint32_t bit_depth,
+                         int64_t* out_vals, uint64_t* out_counts);
+int32_t fbk_query_expr_bsi(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
+                           uint32_t n_shards, uint32_t agg, const fbk_batch* batch, const uint32_t* base_rows, uint32_t bit_depth,
+                           fbk_query** out_query);
 
 
 /* fragment.rows(start, filters...) (fragment.go:2465-2486; executeRowsShard, executor.go:4077-4182): which of

@@ -354,7 +354,7 @@ class Executor {
   explicit Executor(Index& idx) : idx_(idx) {}
 
   // A call tree (Intersect / Union / Difference / Xor / Not over rows, BSI conditions and subtrees) is compiled into leaves plus a
-  // postfix program and evaluated in ONE fbk_expr_eval / fbk_expr_count launch; false: node by node, one fbk_setop / fbk_bsi_range
+  // postfix program and evaluated in ONE fbk_expr_eval / fbk_expr_count / fbk_expr_bsi_agg launch; false: node by node, one fbk_setop / fbk_bsi_range
   // per node as the reference's recursion does (executeBitmapCallShard, executor.go:1782).  Both give the same rows.
   bool fuse_calls = true;
   // device calls issued so far to evaluate bitmap calls (set operations, range scans, shifts, fused trees, row counts)
@@ -437,7 +437,9 @@ class Executor {
     std::vector<uint32_t> base = base_rows(f);
     std::vector<int64_t> sums(n);
     std::vector<uint64_t> counts(n);
-    if (filter) {
+    if (filter && fuses_aggregate(*filter)) {  // Sum(tree, field=): the filter row is never materialised
+      expr_aggregate(FBK_AGG_SUM, *filter, f, base, sums, counts);
+    } else if (filter) {
       RowSet fr = eval(*filter);
       check(fbk_bsi_sum(idx_.ctx_, f.batch, base.data(), uint32_t(n), f.bit_depth, fr.batch(), fr.rows().data(), sums.data(), counts.data()));
     } else {
@@ -1103,6 +1105,18 @@ class Executor {
     check(fbk_fold_n(idx_.ctx_, fold_op(c.kind), idx_.sets_.at(c.children[0].field).batch, g.data(), shards().size(), uint32_t(c.children.size()), FBK_SETOP_OPTIMIZE, &o, nullptr));
     return fresh(o);
   }
+  // Sum / Min / Max over an operator tree: the aggregate runs in the tree's own launch (fbk_expr_bsi_agg), the rule of Count(tree)
+  // above.  A call over plain rows of one field keeps fbk_fold_n and the aggregate's own call (see kFoldFrom: nothing measured
+  // says the interpreter is ahead on that shape); a plain row or no filter keeps today's single call.
+  bool fuses_aggregate(const Call& c) const { return fuse_calls && is_operator(c.kind) && !plain_rows_of_one_field(c); }
+  void expr_aggregate(uint32_t agg, const Call& filter, const Index::IntField& f, const std::vector<uint32_t>& base, std::vector<int64_t>& vals,
+                      std::vector<uint64_t>& counts) {
+    ExprBuild b;
+    compile_root(filter, b);  // (Shift results and subtrees beyond a limit enter as row leaves)
+    ++library_calls;
+    check(fbk_expr_bsi_agg(idx_.ctx_, b.leaves.data(), uint32_t(b.leaves.size()), b.prog.data(), uint32_t(b.prog.size()), uint32_t(base.size()), agg, f.batch,
+                           base.data(), f.bit_depth, vals.data(), counts.data()));
+  }
   RowSet eval(const Call& c) {
     if (!fuse_calls || !is_operator(c.kind)) return eval_nodes(c);
     return plain_rows_of_one_field(c) ? eval_fold(c) : eval_fused(c);
@@ -1200,7 +1214,9 @@ class Executor {
     std::vector<int64_t> vals(n);
     std::vector<uint64_t> counts(n);
     auto fn = is_min ? fbk_bsi_min : fbk_bsi_max;
-    if (filter) {
+    if (filter && fuses_aggregate(*filter)) {
+      expr_aggregate(is_min ? FBK_AGG_MIN : FBK_AGG_MAX, *filter, f, base, vals, counts);
+    } else if (filter) {
       RowSet fr = eval(*filter);
       check(fn(idx_.ctx_, f.batch, base.data(), uint32_t(n), f.bit_depth, fr.batch(), fr.rows().data(), vals.data(), counts.data()));
     } else {
