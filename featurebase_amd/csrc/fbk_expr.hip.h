@@ -32,12 +32,13 @@ struct alignas(16) ExprLeaf {
   uint32_t pad;
 };
 
-// X = f(X, t) for the instructions kLoad .. kAndnRev, t(q) the operand's word q
-template <class F>
-__device__ __forceinline__ void expr_apply_x(uint32_t op, u64 (&X)[kWordsPerLane], F t) {
+// X = f(X, t) for the instructions kLoad .. kAndnRev, t(q) the operand's word q (N words per thread: 16 in the wavefront
+// evaluator below, 4 in the block-wide one of fbk_expr_topk.hip.h)
+template <int N, class F>
+__device__ __forceinline__ void expr_apply_x(uint32_t op, u64 (&X)[N], F t) {
   if (op == fbk_expr::kXor) {
 #pragma unroll
-    for (int q = 0; q < kWordsPerLane; ++q) X[q] ^= t(q);
+    for (int q = 0; q < N; ++q) X[q] ^= t(q);
   } else {
     // ((X ^ a) | k) & (T ^ b)) ^ c: uniform masks instead of one loop per operation
     const u64 a = (op == fbk_expr::kAndnRev || op == fbk_expr::kOr) ? ~0ull : 0ull;
@@ -45,7 +46,7 @@ __device__ __forceinline__ void expr_apply_x(uint32_t op, u64 (&X)[kWordsPerLane
     const u64 b = (op == fbk_expr::kAndn || op == fbk_expr::kOr) ? ~0ull : 0ull;
     const u64 c = op == fbk_expr::kOr ? ~0ull : 0ull;
 #pragma unroll
-    for (int q = 0; q < kWordsPerLane; ++q) X[q] = ((((X[q] ^ a) | k) & (t(q) ^ b)) ^ c);
+    for (int q = 0; q < N; ++q) X[q] = ((((X[q] ^ a) | k) & (t(q) ^ b)) ^ c);
   }
 }
 

@@ -220,4 +220,28 @@ inline Error plan(const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t
   return Error();
 }
 
+// the containers a lowered program reads per (shard, slot): its instructions with an operand (ops <= kMorXAn)
+inline uint32_t operand_reads(const std::vector<uint32_t>& ins) {
+  uint32_t n = 0;
+  for (uint32_t w : ins) n += (w >> 24) <= kMorXAn ? 1u : 0u;
+  return n;
+}
+
+// Rows of the field per block of k_expr_rows_vs_filter (fbk_expr_topk.hip.h), which evaluates the tree once per block: a block
+// reads L + rpb containers, L = operand_reads(program).  The rule of k_rows_vs_filter's launches — halve while the grid is short
+// of 2048 blocks and more than 64 rows are left, then a multiple of 64, at least 64 — with one more condition: a split is taken
+// only while (chunks - 1) * L <= n_a for the chunks it leads to, so that re-evaluating the tree at most doubles the containers
+// read (chunks * L + n_a <= 2 * n_a + L).  L = 0 is the rule of k_rows_vs_filter itself.
+inline uint32_t rows_per_block(uint32_t n_a, uint32_t n_shards_in_pass, uint32_t L) {
+  auto rounded = [](uint32_t r) { return std::max<uint32_t>(64u, (r + 63u) & ~63u); };
+  uint32_t rpb = n_a;
+  while (rpb > 64 && uint64_t(n_shards_in_pass) * 16 * ((n_a + rpb - 1) / rpb) < 2048) {
+    const uint32_t half = (rpb + 1) / 2, r = rounded(half);
+    const uint64_t chunks = (uint64_t(n_a) + r - 1) / r;
+    if ((chunks - 1) * L > n_a) break;
+    rpb = half;
+  }
+  return rounded(rpb);
+}
+
 }  // namespace fbk_expr

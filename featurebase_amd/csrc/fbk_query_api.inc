@@ -702,9 +702,16 @@ namespace {
 // only; d_total = n_a uint64 on the device (zeroed here).
 // the launches of topn_totals_locked on row lists that are already on the device (a prepared TopN keeps them and the
 // pass buffers): ra [n_shards][n_a], rf [n_shards] or nullptr; dshard / dcards / dsrc sized for pass_shards
+//
+// The filter comes from one of two sources: a row per shard of a batch (filter, d_rf), or a call tree (tree: an uploaded ExprProgram,
+// fbk_expr_topk_api.inc) that the counting kernel evaluates itself (k_expr_rows_vs_filter).  With a tree, dsrc holds n_shards words
+// (not pass_shards) and receives every shard's filter count from the counting launch; it may be nullptr when nothing needs them.
+struct ExprProgram;
+int32_t expr_rows_launch(fbk_ctx* ctx, ExprProgram& P, const fbk_batch* a, const uint32_t* d_ra, uint32_t n_a, uint32_t p0, uint32_t pn, u64* dshard, u64* dsrc);
+
 int32_t topn_totals_enqueue(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* d_ra, uint32_t n_a, const fbk_batch* filter, const uint32_t* d_rf, uint32_t n_shards,
                             uint64_t min_threshold, uint64_t tanimoto_threshold, uint64_t pass_shards, u64* dshard, u64* dcards, u64* dsrc, u64* d_total,
-                            const Slot* recs = nullptr, uint32_t cand_n = 0, u64* d_cand = nullptr) {
+                            const Slot* recs = nullptr, uint32_t cand_n = 0, u64* d_cand = nullptr, ExprProgram* tree = nullptr) {
   // cand_n > 0 (the reference's TopN with 0 < n < n_a, option topn_semantics = 1): d_cand [n_a] gets 1 for every row some
   // shard's fragment.top(N = cand_n) would return (k_topn_candidates, pass 1 of executeTopN); the caller masks the totals
   // with it (k_topn_mask) — after the reduce over the members when there are several.  Needs dcards / dsrc with a filter.
@@ -712,13 +719,24 @@ int32_t topn_totals_enqueue(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* d_
   if (cands) HIP_TRY(hipMemsetAsync(d_cand, 0, uint64_t(n_a) * 8, ctx->stream));
   // per-shard counts in passes of <= 1 GiB, summed over the shards into d_total (executeTopKShard's
   // per-shard counts merged by AddBSI / Pairs.Add in the reference's reduce)
-  const bool thresholds = min_threshold > 0 || (tanimoto_threshold > 0 && filter);
+  const bool thresholds = min_threshold > 0 || (tanimoto_threshold > 0 && (filter || tree));
   HIP_TRY(hipMemsetAsync(d_total, 0, uint64_t(n_a) * 8, ctx->stream));
+  if (tree && dsrc) HIP_TRY(hipMemsetAsync(dsrc, 0, uint64_t(n_shards) * 8, ctx->stream));
   for (uint64_t p0 = 0; p0 < n_shards; p0 += pass_shards) {
     const uint32_t pn = uint32_t(std::min<uint64_t>(pass_shards, n_shards - p0));
     const uint32_t* ra = d_ra + p0 * n_a;
     const uint64_t n = uint64_t(pn) * n_a;
-    if (filter) {
+    if (tree) {
+      HIP_TRY(hipMemsetAsync(dshard, 0, n * 8, ctx->stream));
+      u64* src = dsrc ? dsrc + p0 : nullptr;  // (callers with thresholds or candidates pass one)
+      if (int32_t rc = expr_rows_launch(ctx, *tree, a, ra, n_a, uint32_t(p0), pn, dshard, src)) return rc;
+      if (thresholds || cands) hipLaunchKernelGGL(fbk::k_row_cardinality, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, a->d_slots, ra, n, dcards);
+      if (cands)
+        hipLaunchKernelGGL(fbk::k_topn_candidates, dim3(pn), dim3(256), 0, ctx->stream, dshard, dcards, src, n_a, cand_n, u64(min_threshold), u64(tanimoto_threshold), 1, d_cand);
+      if (thresholds)
+        hipLaunchKernelGGL(fbk::k_topn_filter, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, dshard, dcards, src, n, n_a, u64(min_threshold),
+                           u64(tanimoto_threshold));
+    } else if (filter) {
       HIP_TRY(hipMemsetAsync(dshard, 0, n * 8, ctx->stream));
       uint32_t rpb = n_a;
       while (rpb > 64 && uint64_t(pn) * 16 * ((n_a + rpb - 1) / rpb) < 2048) rpb = (rpb + 1) / 2;

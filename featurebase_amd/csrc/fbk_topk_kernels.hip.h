@@ -37,71 +37,38 @@ __global__ void __launch_bounds__(256) k_resolve_rows(const Slot* __restrict__ s
   recs[idx] = slots[(uint64_t)rows[unit * n_per + i] * kSlots + slot];
 }
 
-__global__ void __launch_bounds__(256, 8) k_rows_vs_filter(const Slot* __restrict__ slotsA, const uint8_t* __restrict__ arenaA,
-                                                          const uint32_t* __restrict__ rowsA, uint32_t nA,
-                                                          const Slot* __restrict__ slotsF, const uint8_t* __restrict__ arenaF,
-                                                          const uint32_t* __restrict__ rowsF, uint32_t n_shards,
-                                                          uint32_t rows_per_block, u64* __restrict__ out_shard, const Slot* __restrict__ recs) {
-  __shared__ u64 F[kWords];         // the filter container as a bitmap
-  __shared__ uint32_t rank[kWords + 1];  // rank[w] = popcount(F[0..w))
-  __shared__ uint32_t s_part[4];
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const uint32_t chunks = (nA + rows_per_block - 1) / rows_per_block;
-  uint32_t b = xcd_swizzle(blockIdx.x, gridDim.x);  // (shard, slot, chunk of rows): a shard's blocks on one XCD
-  const uint32_t chunk = b % chunks;
-  b /= chunks;
-  const uint32_t slot = b & 15u;
-  const uint32_t shard = b >> 4;
-  if (shard >= n_shards) return;
-  // The descriptors of the block's first 64 rows hang off a chain of dependent loads (row index -> descriptor)
-  // just like the filter container (row index -> descriptor -> payload): both chains start here, side by side.
-  const uint32_t i_begin = chunk * rows_per_block, i_end = min(nA, i_begin + rows_per_block);
-  const uint32_t* arow = rowsA + (uint64_t)shard * nA;
-  Slot first_mine;
-  first_mine.off = 0;
-  first_mine.len = 0;
-  first_mine.tn = 0;
-  // (a prepared query's resolved row records, k_resolve_rows: the nA descriptors of this (shard, slot) side by side)
-  const Slot* srec = recs ? recs + ((uint64_t)shard * kSlots + slot) * nA : nullptr;
-  if (i_begin + lane < i_end) first_mine = srec ? srec[i_begin + lane] : slotsA[(uint64_t)arow[i_begin + lane] * kSlots + slot];
-  const Slot sf = slotsF[(uint64_t)rowsF[shard] * kSlots + slot];
-  const uint32_t nf = slot_n(sf);
-  if (nf == 0) return;  // nothing can intersect at this slot (block-uniform)
-  const bool f_full = nf == 65536u;
-  if (!f_full) {
-    // ---- filter -> LDS bitmap (wave 0 decodes arrays / runs in place) + rank table ----
-    if (slot_type(sf) == kTypeBitmap) {
-      const ulonglong2* q = reinterpret_cast<const ulonglong2*>(arenaF + sf.off);
-      reinterpret_cast<ulonglong2*>(F)[t] = q[t];
-      reinterpret_cast<ulonglong2*>(F)[256 + t] = q[256 + t];
-    } else if (t < kWave) {
-      u64 f[kWordsPerLane];
-      frag_load(sf, arenaF, t, F, f);
-      lds_write_frag(F, t, f);
-    }
-    __syncthreads();
-    // exclusive prefix popcount over 1024 words: 4 words per thread, wave scan, wave offsets
-    const uint32_t p0 = __popcll(F[4 * t]), p1 = __popcll(F[4 * t + 1]), p2 = __popcll(F[4 * t + 2]), p3 = __popcll(F[4 * t + 3]);
-    const uint32_t mine = p0 + p1 + p2 + p3;
-    uint32_t incl = mine;
+// rank[w] = popcount(F[0..w)) for the 1024 words of the filter bitmap in LDS, rank[kWords] = |F|: an exclusive prefix popcount, 4
+// words per thread, wave scan, wave offsets.  All 256 threads; F is complete and visible when it is called (the caller's barrier),
+// rank is when it returns.
+__device__ __forceinline__ void rows_filter_rank(const u64* F, uint32_t* rank, uint32_t* s_part, int t, int lane, int wv) {
+  const uint32_t p0 = __popcll(F[4 * t]), p1 = __popcll(F[4 * t + 1]), p2 = __popcll(F[4 * t + 2]), p3 = __popcll(F[4 * t + 3]);
+  const uint32_t mine = p0 + p1 + p2 + p3;
+  uint32_t incl = mine;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t v = __shfl_up(incl, o, kWave);
-      if (lane >= o) incl += v;
-    }
-    if (lane == 63) s_part[wv] = incl;
-    __syncthreads();
-    uint32_t base = incl - mine;
-    for (int k = 0; k < wv; ++k) base += s_part[k];
-    rank[4 * t] = base;
-    rank[4 * t + 1] = base + p0;
-    rank[4 * t + 2] = base + p0 + p1;
-    rank[4 * t + 3] = base + p0 + p1 + p2;
-    if (t == 255) rank[kWords] = base + mine;
-    __syncthreads();
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t v = __shfl_up(incl, o, kWave);
+    if (lane >= o) incl += v;
   }
+  if (lane == 63) s_part[wv] = incl;
+  __syncthreads();
+  uint32_t base = incl - mine;
+  for (int k = 0; k < wv; ++k) base += s_part[k];
+  rank[4 * t] = base;
+  rank[4 * t + 1] = base + p0;
+  rank[4 * t + 2] = base + p0 + p1;
+  rank[4 * t + 3] = base + p0 + p1 + p2;
+  if (t == 255) rank[kWords] = base + mine;
+  __syncthreads();
+}
+
+// Everything of k_rows_vs_filter after "the filter is in LDS", shared with k_expr_rows_vs_filter (fbk_expr_topk.hip.h), whose block
+// computes F from a call tree instead of loading it: rows [i_begin, i_end) of the field at (shard, slot) stream past F (1024 words)
+// and rank (kWords + 1 entries) in their encoded form; out_shard[shard * nA + i] += |row i ∩ F|.  nf = |F| (not 0); f_full: nf ==
+// 65536, F and rank are not read.  first_mine: lane l's descriptor of row i_begin + l, requested by the caller before it built F.
+__device__ __forceinline__ void rows_stream_past_filter(const u64* F, const uint32_t* rank, bool f_full, uint32_t nf, const Slot* __restrict__ slotsA,
+                                                        const uint8_t* __restrict__ arenaA, const uint32_t* __restrict__ arow, const Slot* __restrict__ srec,
+                                                        uint32_t nA, uint32_t slot, uint32_t shard, uint32_t i_begin, uint32_t i_end, const Slot& first_mine,
+                                                        int lane, int wv, u64* __restrict__ out_shard) {
   const uint32_t* F32 = reinterpret_cast<const uint32_t*>(F);
   auto rank_of = [&](uint32_t x) -> uint32_t {  // bits of F below position x (0 <= x <= 65536)
     const uint32_t w = x >> 6;
@@ -274,6 +241,56 @@ __global__ void __launch_bounds__(256, 8) k_rows_vs_filter(const Slot* __restric
     // loads still in flight target registers the compiler is about to reuse
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
+}
+
+__global__ void __launch_bounds__(256, 8) k_rows_vs_filter(const Slot* __restrict__ slotsA, const uint8_t* __restrict__ arenaA,
+                                                          const uint32_t* __restrict__ rowsA, uint32_t nA,
+                                                          const Slot* __restrict__ slotsF, const uint8_t* __restrict__ arenaF,
+                                                          const uint32_t* __restrict__ rowsF, uint32_t n_shards,
+                                                          uint32_t rows_per_block, u64* __restrict__ out_shard, const Slot* __restrict__ recs) {
+  __shared__ u64 F[kWords];         // the filter container as a bitmap
+  __shared__ uint32_t rank[kWords + 1];  // rank[w] = popcount(F[0..w))
+  __shared__ uint32_t s_part[4];
+  const int t = threadIdx.x;
+  const int lane = t & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const uint32_t chunks = (nA + rows_per_block - 1) / rows_per_block;
+  uint32_t b = xcd_swizzle(blockIdx.x, gridDim.x);  // (shard, slot, chunk of rows): a shard's blocks on one XCD
+  const uint32_t chunk = b % chunks;
+  b /= chunks;
+  const uint32_t slot = b & 15u;
+  const uint32_t shard = b >> 4;
+  if (shard >= n_shards) return;
+  // The descriptors of the block's first 64 rows hang off a chain of dependent loads (row index -> descriptor)
+  // just like the filter container (row index -> descriptor -> payload): both chains start here, side by side.
+  const uint32_t i_begin = chunk * rows_per_block, i_end = min(nA, i_begin + rows_per_block);
+  const uint32_t* arow = rowsA + (uint64_t)shard * nA;
+  Slot first_mine;
+  first_mine.off = 0;
+  first_mine.len = 0;
+  first_mine.tn = 0;
+  // (a prepared query's resolved row records, k_resolve_rows: the nA descriptors of this (shard, slot) side by side)
+  const Slot* srec = recs ? recs + ((uint64_t)shard * kSlots + slot) * nA : nullptr;
+  if (i_begin + lane < i_end) first_mine = srec ? srec[i_begin + lane] : slotsA[(uint64_t)arow[i_begin + lane] * kSlots + slot];
+  const Slot sf = slotsF[(uint64_t)rowsF[shard] * kSlots + slot];
+  const uint32_t nf = slot_n(sf);
+  if (nf == 0) return;  // nothing can intersect at this slot (block-uniform)
+  const bool f_full = nf == 65536u;
+  if (!f_full) {
+    // ---- filter -> LDS bitmap (wave 0 decodes arrays / runs in place) + rank table ----
+    if (slot_type(sf) == kTypeBitmap) {
+      const ulonglong2* q = reinterpret_cast<const ulonglong2*>(arenaF + sf.off);
+      reinterpret_cast<ulonglong2*>(F)[t] = q[t];
+      reinterpret_cast<ulonglong2*>(F)[256 + t] = q[256 + t];
+    } else if (t < kWave) {
+      u64 f[kWordsPerLane];
+      frag_load(sf, arenaF, t, F, f);
+      lds_write_frag(F, t, f);
+    }
+    __syncthreads();
+    rows_filter_rank(F, rank, s_part, t, lane, wv);
+  }
+  rows_stream_past_filter(F, rank, f_full, nf, slotsA, arenaA, arow, srec, nA, slot, shard, i_begin, i_end, first_mine, lane, wv, out_shard);
 }
 
 // ---- TopK / TopN selection on the device ------------------------------------------------------

@@ -185,6 +185,9 @@ SIGNATURES = {
     "fbk_query_expr": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_expr_bsi_agg": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "fbk_query_expr_bsi": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vpp]),
+    "fbk_expr_row_counts": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "fbk_expr_topk": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
+    "fbk_expr_topn": (C.c_int32, [_vp, C.POINTER(ExprLeaf), C.c_uint32, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32, _vp]),
     "fbk_query_count_matrix": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_query_fold_intersection_count": (C.c_int32, [_vp, C.c_int32, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vpp]),
     "fbk_query_bsi_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_int32, C.c_int64, _vp, _vp, _vpp]),

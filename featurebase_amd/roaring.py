@@ -1102,6 +1102,49 @@ class Context:
     def expr_bsi_max(self, leaves: Sequence[ExprLeaf], prog, batch: Batch, base_rows, bit_depth: int, n_shards: Optional[int] = None):
         return self.expr_bsi_agg(L.AGG_MAX, leaves, prog, batch, base_rows, bit_depth, n_shards)
 
+    def expr_row_counts(self, leaves: Sequence[ExprLeaf], prog, a: Batch, rows_a, per_shard: bool = False, filter_counts: bool = False):
+        """rows_a: [n_shards, n_a]; totals [n_a] of |row ∩ tree| summed over the shards, in the tree's own launch — equal to
+        count_matrix(a, rows_a, F, rows_f) with expr_eval's row F as the single B row.  per_shard / filter_counts add the
+        [n_shards, n_a] counts and the tree's per-shard cardinalities (expr_count) to the returned tuple."""
+        ra = np.ascontiguousarray(rows_a, dtype=np.uint32)
+        n_shards, n_a = ra.shape
+        arr, n, pr, n_shards = self._expr_args(leaves, prog, n_shards)
+        tot = np.zeros(n_a, dtype=np.uint64)
+        ps = np.zeros((n_shards, n_a), dtype=np.uint64) if per_shard else None
+        fc = np.zeros(n_shards, dtype=np.uint64) if filter_counts else None
+        L.check(self.lib.fbk_expr_row_counts(self.h, arr, n, pr.ctypes.data, pr.size, a.h if a is not None else None, ra.ctypes.data, n_a, n_shards,
+                                             tot.ctypes.data, ps.ctypes.data if per_shard else None, fc.ctypes.data if filter_counts else None))
+        if not per_shard and not filter_counts:
+            return tot
+        return (tot,) + ((ps,) if per_shard else ()) + ((fc,) if filter_counts else ())
+
+    def expr_topk(self, leaves: Sequence[ExprLeaf], prog, a: Batch, rows_a, k: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """topk with the call tree as the filter, in the tree's own launch (equal to topk over expr_eval's row)."""
+        ra = np.ascontiguousarray(rows_a, dtype=np.uint32)
+        n_shards, n_a = ra.shape
+        arr, n, pr, n_shards = self._expr_args(leaves, prog, n_shards)
+        cap = n_a if k == 0 else min(k, n_a)
+        idx = np.zeros(max(cap, 1), dtype=np.uint32)
+        cnt = np.zeros(max(cap, 1), dtype=np.uint64)
+        got = C.c_uint32()
+        L.check(self.lib.fbk_expr_topk(self.h, arr, n, pr.ctypes.data, pr.size, a.h if a is not None else None, ra.ctypes.data, n_a, n_shards, k,
+                                       idx.ctypes.data, cnt.ctypes.data, cap, C.byref(got)))
+        return idx[: got.value].copy(), cnt[: got.value].copy()
+
+    def expr_topn(self, leaves: Sequence[ExprLeaf], prog, a: Batch, rows_a, n: int = 0, min_threshold: int = 0,
+                  tanimoto_threshold: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """topn with the call tree as the source row, in the tree's own launch (equal to topn over expr_eval's row)."""
+        ra = np.ascontiguousarray(rows_a, dtype=np.uint32)
+        n_shards, n_a = ra.shape
+        arr, nl, pr, n_shards = self._expr_args(leaves, prog, n_shards)
+        cap = n_a if n == 0 else min(n, n_a)
+        idx = np.zeros(max(cap, 1), dtype=np.uint32)
+        cnt = np.zeros(max(cap, 1), dtype=np.uint64)
+        got = C.c_uint32()
+        L.check(self.lib.fbk_expr_topn(self.h, arr, nl, pr.ctypes.data, pr.size, a.h if a is not None else None, ra.ctypes.data, n_a, n_shards, n,
+                                       min_threshold, tanimoto_threshold, idx.ctypes.data, cnt.ctypes.data, cap, C.byref(got)))
+        return idx[: got.value].copy(), cnt[: got.value].copy()
+
     def query_expr_bsi(self, agg: int, leaves: Sequence[ExprLeaf], prog, batch: Batch, base_rows, bit_depth: int, n_shards: Optional[int] = None) -> Query:
         """expr_bsi_agg as a launch-only query: read() = (values, counts).  AGG_SUM runs may go to / accumulate into a caller's
         device buffer of 24 bytes per shard ({psum, nsum, count})."""

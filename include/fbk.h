@@ -60,7 +60,8 @@ extern "C" {
  *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
  *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free; fbk_bsi_sort;
  *      fbk_extract_open_columns; fbk_bsi_quantiles; fbk_bsi_percentile; fbk_bsi_distinct_rows;
- *      fbk_expr_count / fbk_expr_eval / fbk_query_expr; fbk_expr_bsi_agg / fbk_query_expr_bsi.
+ *      fbk_expr_count / fbk_expr_eval / fbk_query_expr; fbk_expr_bsi_agg / fbk_query_expr_bsi; fbk_expr_row_counts / fbk_expr_topk /
+ *      fbk_expr_topn.
  *   5 (round 5): + fbk_topn_partials, options topn_semantics, matrix_shadow_arena_x.  CHANGED: fbk_topn / fbk_query_topn /
  *      fbk_group_topn with 0 < n < n_a return the reference's two-pass answer by default (topn_semantics = 1; = 0 restores
  *      round 4's exact top n of fbk_topn; round 4's per-member candidate rule of fbk_group_topn is gone — it was neither);
@@ -1024,6 +1025,37 @@ int32_t fbk_expr_bsi_agg(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_l
 int32_t fbk_query_expr_bsi(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
                            uint32_t n_shards, uint32_t agg, const fbk_batch* batch, const uint32_t* base_rows, uint32_t bit_depth,
                            fbk_query** out_query);
+
+/* The counting operators over a call tree, in the tree's own launch: SELECT f, COUNT(*) ... WHERE <tree> GROUP BY f [ORDER BY
+ * count DESC LIMIT k] — TopK(f, filter=<tree>), TopN(f, <tree>, n=), GroupBy(Rows(f), filter=<tree>).  The reference evaluates
+ * the filter per shard (executeTopK / executeTopN -> executeBitmapCallShard) and counts every row of the field against it (doTopK,
+ * executor.go:2705-2746; fragment.top, fragment.go:1317-1437); fbk_expr_eval followed by fbk_topk / fbk_topn / fbk_count_matrix
+ * does the same with the filter row written out as 8 KiB cells and read back per block.  Here every block of the counting kernel
+ * computes the filter container itself from the lowered tree and keeps it in LDS (k_expr_rows_vs_filter): one
+ * upload for the tree, one for the field's rows, no output batch, one synchronisation.
+ *   leaves / prog / n_shards and every tree error and limit: as fbk_expr_count (n_shards <= 2^26).
+ *   a / rows_a / n_a   the field as fbk_topk takes it: rows_a[s * n_a + i] = row i of the field in shard s, n_a <= 2^22.
+ *   fbk_expr_row_counts   out_total [n_a], out_per_shard [n_shards * n_a] or NULL, out_filter_counts [n_shards] or NULL: bit for
+ *                    bit out_total / out_per_shard of fbk_count_matrix(a, rows_a, n_a, F, rows_f, 1, ...) with F the batch
+ *                    fbk_expr_eval gives for the tree, and the counts of fbk_expr_count.  With out_per_shard all shards are one
+ *                    pass (n_shards * n_a * 8 bytes on the device); a rank of a cluster reduces these with its peers' itself.
+ *   fbk_expr_topk / fbk_expr_topn   bit for bit fbk_topk / fbk_topn with that F as the filter: ordering, zero counts dropped, k /
+ *                    n = 0 for all, min_threshold, tanimoto_threshold (<= 100), option topn_semantics and its candidate pass, the
+ *                    device sort past 4096 rows (option topk_device_sort), FBK_E_CAPACITY with *out_n = what is needed.
+ *   FBK_E_INVALID before anything is launched, the context stays usable: a tree error, NULL a, NULL rows_a with n_a and n_shards
+ *                    > 0, a row index past the batch, n_a > 2^22, n_shards > 2^26, a NULL output that is not optional.
+ *   n_shards == 0    FBK_OK: zero totals (fbk_expr_row_counts), *out_n = 0.  n_a == 0: FBK_OK, nothing written but *out_n = 0.
+ * Not offered: a prepared fbk_query_* form; fbk_topn_partials / fbk_group_topn over a tree (out_per_shard and out_total are what a
+ * rank needs to reduce counts itself); k_expr_slot on the block-wide evaluator. */
+int32_t fbk_expr_row_counts(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
+                            const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, uint32_t n_shards, uint64_t* out_total,
+                            uint64_t* out_per_shard, uint64_t* out_filter_counts);
+int32_t fbk_expr_topk(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
+                      const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, uint32_t n_shards, uint32_t k, uint32_t* out_index,
+                      uint64_t* out_count, uint32_t cap, uint32_t* out_n);
+int32_t fbk_expr_topn(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog,
+                      const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, uint32_t n_shards, uint32_t n, uint64_t min_threshold,
+                      uint64_t tanimoto_threshold, uint32_t* out_index, uint64_t* out_count, uint32_t cap, uint32_t* out_n);
 
 
 /* fragment.rows(start, filters...) (fragment.go:2465-2486; executeRowsShard, executor.go:4077-4182): which of

@@ -669,7 +669,13 @@ class Executor {
     std::vector<uint32_t> idx(cap);
     std::vector<uint64_t> cnt(cap);
     uint32_t got = 0;
-    if (filter) {
+    if (filter && fuses_topk(*filter, n, nr)) {  // TopK(field, filter=tree): the filter row is never materialised (fbk_expr_topk)
+      ExprBuild b;
+      compile_root(*filter, b);
+      ++library_calls;
+      check(fbk_expr_topk(idx_.ctx_, b.leaves.data(), uint32_t(b.leaves.size()), b.prog.data(), uint32_t(b.prog.size()), f.batch, rows_a.data(), uint32_t(nr),
+                          uint32_t(n), uint32_t(cap == nr ? 0 : cap), idx.data(), cnt.data(), cap, &got));
+    } else if (filter) {
       RowSet fr = eval(*filter);
       check(fbk_topk(idx_.ctx_, f.batch, rows_a.data(), uint32_t(nr), fr.batch(), fr.rows().data(), uint32_t(n), uint32_t(cap == nr ? 0 : cap),
                      idx.data(), cnt.data(), cap, &got));
@@ -1109,6 +1115,11 @@ class Executor {
   // above.  A call over plain rows of one field keeps fbk_fold_n and the aggregate's own call (see kFoldFrom: nothing measured
   // says the interpreter is ahead on that shape); a plain row or no filter keeps today's single call.
   bool fuses_aggregate(const Call& c) const { return fuse_calls && is_operator(c.kind) && !plain_rows_of_one_field(c); }
+  // TopK / TopN over an operator tree: fbk_expr_topk where its launch evaluates the tree ONCE per (shard, slot) — a field of at most
+  // 64 rows, or 128 shards and more (k_expr_rows_vs_filter splits a longer field over several blocks while the grid is short of
+  // 2048, and every block evaluates the tree again: measured 2-4 % behind fbk_expr_eval + fbk_topk at 96 shards x 256 / 1024 rows,
+  // 10-19 % ahead at 64 rows and 2 % ahead at 1024 shards x 1024 rows).  Everything else keeps the pair.
+  bool fuses_topk(const Call& c, size_t n_shards, size_t n_rows) const { return fuses_aggregate(c) && (n_rows <= 64 || n_shards >= 128); }
   void expr_aggregate(uint32_t agg, const Call& filter, const Index::IntField& f, const std::vector<uint32_t>& base, std::vector<int64_t>& vals,
                       std::vector<uint64_t>& counts) {
     ExprBuild b;

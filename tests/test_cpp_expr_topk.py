@@ -1,0 +1,35 @@
+"""Executor::TopK / TopN with fuse_calls (include/fbk_executor.hpp: the filter tree and the counting as ONE fbk_expr_topk) against
+the two-step path, over a seeded index in tests/cpp/test_expr_topk.cpp, built the way tests/test_cpp_expr_agg.py builds its program;
+the compile check runs everywhere, the run needs the GPU."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "test_expr_topk.cpp")
+BIN = os.path.join(ROOT, "build", "test_expr_topk")
+
+
+def compile_it():
+    import __graft_entry__ as g
+
+    g.build()
+    os.makedirs(os.path.dirname(BIN), exist_ok=True)
+    lib = os.path.join(ROOT, "featurebase_amd", "csrc")
+    subprocess.check_call(
+        ["g++", "-std=c++17", "-O2", "-Wall", "-pthread", "-I", os.path.join(ROOT, "include"), SRC, "-L", lib, "-lfbk", f"-Wl,-rpath,{lib}", "-Wl,-rpath-link,/opt/rocm/lib", "-o", BIN]
+    )
+
+
+def test_expr_topk_compiles():
+    compile_it()
+    assert os.path.exists(BIN)
+
+
+@pytest.mark.gpu
+def test_expr_topk_on_gpu():
+    compile_it()
+    out = subprocess.run([BIN], capture_output=True, text=True, timeout=600, env={**os.environ, "FBK_TEST_SEED": "4242"})
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "expr topk ok" in out.stdout
