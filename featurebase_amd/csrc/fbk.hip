@@ -1399,6 +1399,7 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_quantile_api.inc"
 #include "fbk_distinct_rows_api.inc"
 #include "fbk_expr_api.inc"
+#include "fbk_topn_api.inc"
 #include "fbk_expr_topk_api.inc"
 #include "fbk_prepared_api.inc"
 #include "fbk_wire_parse.h"

@@ -565,8 +565,7 @@ int32_t fbk_group_topn(fbk_group* g, const fbk_topn_args* per_member, uint32_t n
   if (int32_t rc = group_check(g)) return rc;
   GroupScope gs(g);
   if (!per_member || !out_n || (cap && (!out_index || !out_count))) return fail(FBK_E_INVALID, "NULL argument");
-  if (n_a > (1u << 22)) return fail(FBK_E_INVALID, "topk: at most 2^22 rows");
-  if (tanimoto_threshold > 100) return fail(FBK_E_INVALID, "topn: Tanimoto threshold is a percentage (0..100)");
+  if (int32_t rc = topn_args_ok(n_a, tanimoto_threshold)) return rc;
   *out_n = 0;
   if (n_a == 0) return FBK_OK;
   std::lock_guard<std::mutex> lk(g->mu);
@@ -597,7 +596,8 @@ int32_t fbk_group_topn(fbk_group* g, const fbk_topn_args* per_member, uint32_t n
       if (hipMemsetAsync(part, 0, words * 8, c->stream) != hipSuccess) rc = fail(FBK_E_HIP, "group topn: memset failed");
       continue;
     }
-    rc = topn_totals_locked(c, a.a, a.rows_a, n_a, a.filter, a.rows_f, a.n_shards, min_threshold, tanimoto_threshold, part, cand_n, cand_n ? part + n_a : nullptr);
+    TopnBuffers scratch;  // (totals and flags go to `part`; not masked: the flags of all members are reduced first)
+    rc = topn_totals_locked(c, a.a, a.rows_a, n_a, a.filter, a.rows_f, a.n_shards, min_threshold, tanimoto_threshold, cand_n, scratch, /*mask=*/false, part, part + n_a);
   }
   std::vector<uint64_t> tot(words);
   if (!rc) rc = group_reduce(g, words, tot.data());
@@ -606,19 +606,7 @@ int32_t fbk_group_topn(fbk_group* g, const fbk_topn_args* per_member, uint32_t n
     return rc;
   }
   // ---- candidates only, then order (Pairs.Less by count; ties by row index ascending, as fbk_topn), drop empty rows, trim to n
-  std::vector<uint32_t> order;
-  order.reserve(n_a);
-  for (uint32_t k = 0; k < n_a; ++k)
-    if (tot[k] && (!cand_n || tot[n_a + k])) order.push_back(k);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return tot[x] > tot[y]; });
-  const uint32_t want = top_n ? std::min<uint32_t>(top_n, uint32_t(order.size())) : uint32_t(order.size());
-  *out_n = want;
-  if (want > cap) return fail(FBK_E_CAPACITY, "topn: " + std::to_string(want) + " results, buffers hold " + std::to_string(cap));
-  for (uint32_t j = 0; j < want; ++j) {
-    out_index[j] = order[j];
-    out_count[j] = tot[order[j]];
-  }
-  return FBK_OK;
+  return topn_order_host("topn", tot.data(), cand_n ? tot.data() + n_a : nullptr, n_a, top_n, out_index, out_count, cap, out_n);
 } FBK_ABI_CATCH_GROUP(g)
 
 /* Message and status code of the last failing fbk_group_* call on THIS group, copied into a caller buffer

@@ -37,13 +37,14 @@ struct fbk_query {
   uint32_t out_flags = 0;   // FBK_SETOP_OPTIMIZE: the fold encodes in its epilogue
   DevBuf dprog;             // BSI Range: the plane program
   uint32_t prog_len = 0;
-  // TopN: thresholds, the n asked for, the pieces of the on-device ordering (all sized at prepare)
-  uint64_t min_threshold = 0, tanimoto_threshold = 0;
-  uint32_t top_n = 0;
-  uint32_t cand_n = 0;  // > 0: the reference's candidate pass with this n (topn_cand_n at prepare), flags in dcand
-  DevBuf dpass, dcards, dsrc, dsk, dval, dsv, dtmp, dnz, dcand;
-  size_t sort_tmp_bytes = 0;
-  uint64_t pass_shards = 0;
+  // TopN (fbk_topn_api.inc): the n asked for, the pass buffers with their plan (thresholds, the candidate pass's n under the
+  // semantics in force at prepare; totals in `result`) and the scratch of the on-device ordering — all sized at prepare
+  struct Topn {
+    uint32_t top_n = 0;
+    TopnBuffers buf;
+    TopnSort sort;
+  };
+  std::unique_ptr<Topn> topn;
   bool ran = false;
   void* last_out = nullptr;  // where the last run wrote (result.p or the caller's buffer)
   // folds and TopN: the descriptors of every (group / shard, slot) side by side (k_resolve_rows), resolved on the first run and
@@ -380,8 +381,7 @@ int32_t fbk_query_topn(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a,
   FBK_ENTER(ctx);
   if (!ctx || !a || !out_query || !rows_a || (filter && !rows_f)) return fail(FBK_E_INVALID, "NULL argument");
   *out_query = nullptr;
-  if (n_a > (1u << 22)) return fail(FBK_E_INVALID, "topk: at most 2^22 rows");
-  if (tanimoto_threshold > 100) return fail(FBK_E_INVALID, "topn: Tanimoto threshold is a percentage (0..100)");
+  if (int32_t rc = topn_args_ok(n_a, tanimoto_threshold)) return rc;
   if (n_shards == 0 || n_a == 0) return fail(FBK_E_INVALID, "query: empty TopN");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
@@ -394,33 +394,17 @@ int32_t fbk_query_topn(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a,
   q->filter = filter;
   q->n_a = n_a;
   q->n = n_shards;
-  q->top_n = n;
-  q->min_threshold = min_threshold;
-  q->tanimoto_threshold = tanimoto_threshold;
   q->result_bytes = uint64_t(n_a) * 8;
-  q->cand_n = topn_cand_n(ctx, n, n_a, true);  // (the semantics in force when the query is prepared)
-  const bool thresholds = min_threshold > 0 || (tanimoto_threshold > 0 && filter) || q->cand_n;
-  q->pass_shards = std::max<uint64_t>(1, std::min<uint64_t>(n_shards, (uint64_t(ctx->opt.matrix_pass_kb) << 10) / (uint64_t(n_a) * 8)));
+  q->topn.reset(new fbk_query::Topn());
+  q->topn->top_n = n;
+  // (the semantics and option matrix_pass_kb in force when the query is prepared)
+  const fbk_topn_plan::Sizes sizes = topn_plan(ctx, n_a, n_shards, TopnSource{filter}, min_threshold, tanimoto_threshold, topn_cand_n(ctx, n, n_a, true));
   int32_t rc = upload_rows_multi(ctx, {{rows_a, uint64_t(n_shards) * n_a, UINT32_MAX}, {rows_f, filter ? uint64_t(n_shards) : 0, filter ? filter->n_rows : UINT32_MAX}}, q->rows,
                                  q->dr);
   if (!rc) {
     hipError_t e = q->result.alloc(ctx, q->result_bytes);
-    if (e == hipSuccess) e = q->dpass.alloc(ctx, q->pass_shards * n_a * 8);
-    if (e == hipSuccess && thresholds && filter) {
-      e = q->dcards.alloc(ctx, q->pass_shards * n_a * 8);
-      if (e == hipSuccess) e = q->dsrc.alloc(ctx, q->pass_shards * 8);
-    }
-    if (e == hipSuccess && q->cand_n) e = q->dcand.alloc(ctx, uint64_t(n_a) * 8);
-    if (e == hipSuccess) e = q->dsk.alloc(ctx, uint64_t(n_a) * 8);
-    if (e == hipSuccess) e = q->dval.alloc(ctx, uint64_t(n_a) * 4);
-    if (e == hipSuccess) e = q->dsv.alloc(ctx, uint64_t(n_a) * 4);
-    if (e == hipSuccess) e = q->dnz.alloc(ctx, 16);
-    if (e == hipSuccess)
-      e = hipcub::DeviceRadixSort::SortPairsDescending(nullptr, q->sort_tmp_bytes, q->result.as<u64>(), q->dsk.as<u64>(), q->dval.as<uint32_t>(), q->dsv.as<uint32_t>(), int(n_a), 0,
-                                                       64, ctx->stream);
-    if (e == hipSuccess) e = q->dtmp.alloc(ctx, std::max<size_t>(q->sort_tmp_bytes, 16));
-    if (e == hipSuccess) hipLaunchKernelGGL(fbk::k_iota_u32, dim3((n_a + 255) / 256), dim3(256), 0, ctx->stream, q->dval.as<uint32_t>(), n_a);
-    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = q->topn->buf.alloc(ctx, sizes, q->result.as<u64>());
+    if (e == hipSuccess) e = q->topn->sort.alloc(ctx, n_a);
     if (e != hipSuccess) rc = fail(FBK_E_NOMEM, std::string("query: ") + hipGetErrorString(e));
   }
   return query_finish_create(ctx, q, rc, out_query);
@@ -530,23 +514,19 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
       const Slot* recs = nullptr;
       if (q->filter) rc = query_row_records(ctx, q, q->n, q->n_a, &recs);  // (k_rows_vs_filter; without a filter the stored cardinalities answer)
       if (rc) break;
-      rc = topn_totals_enqueue(ctx, q->a, q->dr[0], q->n_a, q->filter, q->filter ? q->dr[1] : nullptr, uint32_t(q->n), q->min_threshold, q->tanimoto_threshold, q->pass_shards,
-                               q->dpass.as<u64>(), q->dcards.as<u64>(), q->dsrc.as<u64>(), q->result.as<u64>(), recs, q->cand_n, q->dcand.as<u64>());
+      TopnSort& s = q->topn->sort;
+      rc = topn_totals_enqueue(ctx, q->a, q->dr[0], TopnSource{q->filter, q->dr[1], recs}, q->topn->buf, /*mask=*/true);
       if (rc) break;
-      if (q->cand_n) hipLaunchKernelGGL(fbk::k_topn_mask, dim3((q->n_a + 255) / 256), dim3(256), 0, ctx->stream, q->result.as<u64>(), q->dcand.as<u64>(), q->n_a);
       if (q->n_a <= fbk::kRankSortMax) {
         // a field of a few thousand rows: every row finds its own rank (one launch; the radix sort's five launches were 30 of
         // the 154 us of TopN(10) over config 3's 64 rows)
-        HIP_TRY(hipMemsetAsync(q->dnz.p, 0, 4, ctx->stream));
-        hipLaunchKernelGGL(fbk::k_rank_sort_desc, dim3((q->n_a + 255) / 256), dim3(256), 0, ctx->stream, q->result.as<u64>(), q->n_a, q->dsk.as<u64>(), q->dsv.as<uint32_t>(),
-                           q->dnz.as<uint32_t>());
+        HIP_TRY(hipMemsetAsync(s.dnz.p, 0, 4, ctx->stream));
+        hipLaunchKernelGGL(fbk::k_rank_sort_desc, dim3((q->n_a + 255) / 256), dim3(256), 0, ctx->stream, q->result.as<u64>(), q->n_a, s.dsk.as<u64>(), s.dsv.as<uint32_t>(),
+                           s.dnz.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
       } else {
-        size_t tb = q->sort_tmp_bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(q->dtmp.p, tb, q->result.as<u64>(), q->dsk.as<u64>(), q->dval.as<uint32_t>(), q->dsv.as<uint32_t>(), int(q->n_a), 0, 64,
-                                                             ctx->stream));
-        hipLaunchKernelGGL(fbk::k_count_nonzero_desc, dim3(1), dim3(1), 0, ctx->stream, q->dsk.as<u64>(), q->n_a, q->dnz.as<uint32_t>());
+        rc = topn_radix_enqueue(ctx, s, q->result.as<u64>(), q->n_a);
       }
-      HIP_TRY(hipGetLastError());
       break;
     }
     default:
@@ -595,16 +575,17 @@ int32_t fbk_query_read(fbk_ctx* ctx, fbk_query* q, void* out0, void* out1) try {
     case kQTopN: {
       // out0 = uint32 {number of results, then that many row indexes}  (1 + min(n, n_a) words, n = 0: 1 + n_a);
       // out1 = uint64 counts of those rows
+      const fbk_query::Topn& t = *q->topn;
       uint32_t nz = 0;
-      HIP_TRY(back.add(&nz, q->dnz.p, 4));
+      HIP_TRY(back.add(&nz, t.sort.dnz.p, 4));
       HIP_TRY(back.finish());
-      const uint32_t want = q->top_n ? std::min(q->top_n, nz) : nz;  // rows without a single common column are not results
+      const uint32_t want = t.top_n ? std::min(t.top_n, nz) : nz;  // rows without a single common column are not results
       uint32_t* idx = static_cast<uint32_t*>(out0);
       if (idx) idx[0] = want;
       if (want) {
         D2H back2(ctx);
-        if (idx) HIP_TRY(back2.add(idx + 1, q->dsv.p, uint64_t(want) * 4));
-        if (out1) HIP_TRY(back2.add(out1, q->dsk.p, uint64_t(want) * 8));
+        if (idx) HIP_TRY(back2.add(idx + 1, t.sort.dsv.p, uint64_t(want) * 4));
+        if (out1) HIP_TRY(back2.add(out1, t.sort.dsk.p, uint64_t(want) * 8));
         HIP_TRY(back2.finish());
       }
       return FBK_OK;

@@ -1,7 +1,7 @@
 // fbk_query_api.inc — host side of the query-level entry points (included by fbk.hip).
-// n-way fold, count matrix (GroupBy / TopK / TopN), Rows, Flip, Shift, and the BSI calls: Range, Sum / Min / Max and the range
-// sums (one frame: BsiShardOperands + download_words), Add, Distinct.  The output batch of the materialising ones is a
-// CellOutput (fbk_output.inc).
+// n-way fold, count matrix (GroupBy, and the launch of k_rows_vs_filter for its TopK shape), Rows, Flip, Shift, and the BSI calls:
+// Range, Sum / Min / Max and the range sums (one frame: BsiShardOperands + download_words), Add, Distinct.  The output batch of the
+// materialising ones is a CellOutput (fbk_output.inc).  TopK / TopN: fbk_topn_api.inc.
 
 namespace {
 
@@ -504,6 +504,17 @@ int32_t fused_program_build(fbk_ctx* ctx, FxProgram& fp, const fbk_batch* a, con
   return FBK_OK;
 }
 
+// THE launch of k_rows_vs_filter (the count matrix's TopK shape below, TopN over a filter row in fbk_topn_api.inc): pn shards,
+// shard s counts rows ra[s][0 .. n_a) of `a` against row rf[s] of `f` into d_out [pn][n_a] (zeroed by the caller); recs: the
+// resolved records of a's rows or nullptr.  The rows per block are fbk_expr::rows_per_block with no tree to re-evaluate (L = 0).
+void launch_rows_vs_filter(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* ra, uint32_t n_a, const fbk_batch* f, const uint32_t* rf, uint32_t pn, u64* d_out,
+                           const Slot* recs) {
+  const uint32_t rpb = fbk_expr::rows_per_block(n_a, pn, 0);
+  const uint32_t chunks = (n_a + rpb - 1) / rpb;
+  hipLaunchKernelGGL(fbk::k_rows_vs_filter, dim3(pn * 16 * chunks), dim3(256), 0, ctx->stream, a->d_slots, a->d_arena, ra, n_a, f->d_slots, f->d_arena, rf, pn, rpb,
+                     d_out, recs);
+}
+
 // d_rows != nullptr: the row lists are already on the device (a prepared query, fbk_query_*): {A, B, filter};
 // then accumulate = true leaves what d_total holds in place and adds to it
 int32_t count_matrix_enqueue_locked(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
@@ -548,12 +559,7 @@ int32_t count_matrix_enqueue_locked(fbk_ctx* ctx, const fbk_batch* a, const uint
     FxProgram pass_program;  // (a pass of a one-shot call, or one of several passes: built, used, dropped)
     if (n_b == 1 && !filter) {
       // many rows x one row (doTopK / fragment.top): the single B row is the filter of k_rows_vs_filter
-      uint32_t rpb = n_a;
-      while (rpb > 64 && uint64_t(pn) * 16 * ((n_a + rpb - 1) / rpb) < 2048) rpb = (rpb + 1) / 2;
-      rpb = std::max<uint32_t>(64, (rpb + 63) & ~63u);
-      const uint32_t chunks = (n_a + rpb - 1) / rpb;
-      hipLaunchKernelGGL(fbk::k_rows_vs_filter, dim3(pn * 16 * chunks), dim3(256), 0, ctx->stream, a->d_slots, a->d_arena,
-                         ra, n_a, b->d_slots, b->d_arena, rb, pn, rpb, d_out, recs_a ? recs_a + uint64_t(p0) * fbk::kSlots * n_a : (const Slot*)nullptr);
+      launch_rows_vs_filter(ctx, a, ra, n_a, b, rb, pn, d_out, recs_a ? recs_a + uint64_t(p0) * fbk::kSlots * n_a : (const Slot*)nullptr);
     } else if (a->dense && b->dense && (!filter || filter->dense) && n_b > 1) {
       // every container a bitmap at a fixed address: the matrix-core kernel (fbk_matrix_mfma.hip.h)
       launch_matrix_dense(ctx, a->d_arena, ra, n_a, b->d_arena, rb, n_b,
@@ -693,215 +699,6 @@ int32_t fbk_count_matrix(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 
-}  // extern "C"
-
-namespace {
-
-// totals[i] = sum over the shards of the count of row i that QUALIFIES in that shard (fragment.top's
-// rules, k_topn_filter): |row ∩ filter_s| with a filter, the stored cardinality without.  Launch
-// only; d_total = n_a uint64 on the device (zeroed here).
-// the launches of topn_totals_locked on row lists that are already on the device (a prepared TopN keeps them and the
-// pass buffers): ra [n_shards][n_a], rf [n_shards] or nullptr; dshard / dcards / dsrc sized for pass_shards
-//
-// The filter comes from one of two sources: a row per shard of a batch (filter, d_rf), or a call tree (tree: an uploaded ExprProgram,
-// fbk_expr_topk_api.inc) that the counting kernel evaluates itself (k_expr_rows_vs_filter).  With a tree, dsrc holds n_shards words
-// (not pass_shards) and receives every shard's filter count from the counting launch; it may be nullptr when nothing needs them.
-struct ExprProgram;
-int32_t expr_rows_launch(fbk_ctx* ctx, ExprProgram& P, const fbk_batch* a, const uint32_t* d_ra, uint32_t n_a, uint32_t p0, uint32_t pn, u64* dshard, u64* dsrc);
-
-int32_t topn_totals_enqueue(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* d_ra, uint32_t n_a, const fbk_batch* filter, const uint32_t* d_rf, uint32_t n_shards,
-                            uint64_t min_threshold, uint64_t tanimoto_threshold, uint64_t pass_shards, u64* dshard, u64* dcards, u64* dsrc, u64* d_total,
-                            const Slot* recs = nullptr, uint32_t cand_n = 0, u64* d_cand = nullptr, ExprProgram* tree = nullptr) {
-  // cand_n > 0 (the reference's TopN with 0 < n < n_a, option topn_semantics = 1): d_cand [n_a] gets 1 for every row some
-  // shard's fragment.top(N = cand_n) would return (k_topn_candidates, pass 1 of executeTopN); the caller masks the totals
-  // with it (k_topn_mask) — after the reduce over the members when there are several.  Needs dcards / dsrc with a filter.
-  const bool cands = cand_n > 0 && d_cand;
-  if (cands) HIP_TRY(hipMemsetAsync(d_cand, 0, uint64_t(n_a) * 8, ctx->stream));
-  // per-shard counts in passes of <= 1 GiB, summed over the shards into d_total (executeTopKShard's
-  // per-shard counts merged by AddBSI / Pairs.Add in the reference's reduce)
-  const bool thresholds = min_threshold > 0 || (tanimoto_threshold > 0 && (filter || tree));
-  HIP_TRY(hipMemsetAsync(d_total, 0, uint64_t(n_a) * 8, ctx->stream));
-  if (tree && dsrc) HIP_TRY(hipMemsetAsync(dsrc, 0, uint64_t(n_shards) * 8, ctx->stream));
-  for (uint64_t p0 = 0; p0 < n_shards; p0 += pass_shards) {
-    const uint32_t pn = uint32_t(std::min<uint64_t>(pass_shards, n_shards - p0));
-    const uint32_t* ra = d_ra + p0 * n_a;
-    const uint64_t n = uint64_t(pn) * n_a;
-    if (tree) {
-      HIP_TRY(hipMemsetAsync(dshard, 0, n * 8, ctx->stream));
-      u64* src = dsrc ? dsrc + p0 : nullptr;  // (callers with thresholds or candidates pass one)
-      if (int32_t rc = expr_rows_launch(ctx, *tree, a, ra, n_a, uint32_t(p0), pn, dshard, src)) return rc;
-      if (thresholds || cands) hipLaunchKernelGGL(fbk::k_row_cardinality, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, a->d_slots, ra, n, dcards);
-      if (cands)
-        hipLaunchKernelGGL(fbk::k_topn_candidates, dim3(pn), dim3(256), 0, ctx->stream, dshard, dcards, src, n_a, cand_n, u64(min_threshold), u64(tanimoto_threshold), 1, d_cand);
-      if (thresholds)
-        hipLaunchKernelGGL(fbk::k_topn_filter, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, dshard, dcards, src, n, n_a, u64(min_threshold),
-                           u64(tanimoto_threshold));
-    } else if (filter) {
-      HIP_TRY(hipMemsetAsync(dshard, 0, n * 8, ctx->stream));
-      uint32_t rpb = n_a;
-      while (rpb > 64 && uint64_t(pn) * 16 * ((n_a + rpb - 1) / rpb) < 2048) rpb = (rpb + 1) / 2;
-      rpb = std::max<uint32_t>(64, (rpb + 63) & ~63u);
-      const uint32_t chunks = (n_a + rpb - 1) / rpb;
-      {
-        KernelSpan span(ctx);
-        hipLaunchKernelGGL(fbk::k_rows_vs_filter, dim3(pn * 16 * chunks), dim3(256), 0, ctx->stream, a->d_slots, a->d_arena, ra, n_a, filter->d_slots, filter->d_arena,
-                           d_rf + p0, pn, rpb, dshard, recs ? recs + p0 * fbk::kSlots * n_a : (const Slot*)nullptr);
-      }
-      if (thresholds || cands) {
-        hipLaunchKernelGGL(fbk::k_row_cardinality, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, a->d_slots, ra, n, dcards);
-        hipLaunchKernelGGL(fbk::k_row_cardinality, dim3(uint32_t((pn + 255) / 256)), dim3(256), 0, ctx->stream, filter->d_slots, d_rf + p0, uint64_t(pn), dsrc);
-      }
-      if (cands)
-        hipLaunchKernelGGL(fbk::k_topn_candidates, dim3(pn), dim3(256), 0, ctx->stream, dshard, dcards, dsrc, n_a, cand_n, u64(min_threshold), u64(tanimoto_threshold), 1, d_cand);
-      if (thresholds) {
-        hipLaunchKernelGGL(fbk::k_topn_filter, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, dshard, dcards, dsrc, n, n_a, u64(min_threshold),
-                           u64(tanimoto_threshold));
-      }
-    } else {
-      hipLaunchKernelGGL(fbk::k_row_cardinality, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, a->d_slots, ra, n, dshard);
-      if (cands)  // no source row: the first cand_n rows of the rank order that reach MinThreshold (fragment.go:1398-1401)
-        hipLaunchKernelGGL(fbk::k_topn_candidates, dim3(pn), dim3(256), 0, ctx->stream, dshard, dshard, (const u64*)nullptr, n_a, cand_n, u64(min_threshold), u64(0), 0, d_cand);
-      if (thresholds)  // no source row: count == cardinality, the rule is count >= MinThreshold
-        hipLaunchKernelGGL(fbk::k_topn_filter, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, dshard, dshard, (const u64*)nullptr, n, n_a,
-                           u64(min_threshold), u64(0));
-    }
-    hipLaunchKernelGGL(fbk::k_reduce_shards, dim3(uint32_t((uint64_t(n_a) + 255) / 256), std::min<uint32_t>(pn, 64)), dim3(256), 0, ctx->stream, dshard, pn,
-                       uint64_t(n_a), d_total);
-  }
-  HIP_TRY(hipGetLastError());
-  return FBK_OK;
-}
-
-int32_t topn_totals_locked(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* filter,
-                           const uint32_t* rows_f, uint32_t n_shards, uint64_t min_threshold, uint64_t tanimoto_threshold, u64* d_total, uint32_t cand_n = 0,
-                           u64* d_cand = nullptr) {
-  if (int32_t rc = check_rows(rows_a, uint64_t(n_shards) * n_a, a->n_rows, "topk rows")) return rc;
-  fbk_batch* aa = const_cast<fbk_batch*>(a);
-  if (int32_t rc = refresh_slots(aa)) return rc;
-  DevBuf drows, dshard, dcards, dsrc;
-  const uint32_t* dr[2] = {nullptr, nullptr};  // field rows and filter rows: one upload
-  if (int32_t rc = upload_rows_multi(ctx, {{rows_a, uint64_t(n_shards) * n_a, UINT32_MAX}, {rows_f, filter ? uint64_t(n_shards) : 0, filter ? filter->n_rows : UINT32_MAX}},
-                                     drows, dr))
-    return rc;
-  const bool thresholds = min_threshold > 0 || (tanimoto_threshold > 0 && filter);
-  const uint64_t pass_bytes = uint64_t(ctx->opt.matrix_pass_kb) << 10;
-  const uint64_t pass_shards = std::max<uint64_t>(1, std::min<uint64_t>(n_shards, pass_bytes / (uint64_t(n_a) * 8)));
-  HIP_TRY(dshard.alloc(ctx, pass_shards * n_a * 8));
-  if ((thresholds || (cand_n && d_cand)) && filter) {
-    HIP_TRY(dcards.alloc(ctx, pass_shards * n_a * 8));
-    HIP_TRY(dsrc.alloc(ctx, pass_shards * 8));
-  }
-  return topn_totals_enqueue(ctx, a, dr[0], n_a, filter, dr[1], n_shards, min_threshold, tanimoto_threshold, pass_shards, dshard.as<u64>(), dcards.as<u64>(), dsrc.as<u64>(),
-                             d_total, nullptr, cand_n, d_cand);
-}
-
-// The n of fragment.top's candidate pass for a TopN of n over n_a rows under the context's semantics (0: no candidate pass —
-// n = 0 asks for every row, n >= n_a cannot fill any shard's heap before its rows run out, topn_semantics = 0 is exact).
-inline uint32_t topn_cand_n(const fbk_ctx* ctx, uint32_t n, uint32_t n_a, bool reference_operator) {
-  return (reference_operator && ctx->opt.topn_semantics == 1 && n > 0 && n < n_a) ? n : 0;
-}
-
-// The ordering step of TopK / TopN over totals that are already on the device (dtot: n_a uint64, this
-// context's stream): count descending, row index ascending inside one count, zero counts dropped, at most k
-// results (k = 0: all).  Synchronises the stream.
-int32_t topn_order_locked(fbk_ctx* ctx, DevBuf& dtot, uint32_t n_a, uint32_t k, uint32_t* out_index, uint64_t* out_count, uint32_t cap, uint32_t* out_n) {
-  DevBuf dsk, dval, dsv, dtmp, dnz;
-  // order: count descending, row index ascending inside one count (BSIData.PivotDescending,
-  // bsi.go:18-62).  A field of a few thousand rows is ordered on the host (32 KB of totals cross
-  // the bus; a device radix sort of 64 keys costs 50 us of launch latency, measured); larger
-  // fields by a stable descending radix sort of (count, index) pairs that start in index order,
-  // and only the winners come back.  FBK_TOPK_DEVICE_SORT=1 / =0 pins the choice (tests).
-  bool device_sort = n_a > 4096;
-  if (ctx->opt.topk_device_sort >= 0) device_sort = ctx->opt.topk_device_sort == 1;
-  if (!device_sort) {
-    std::vector<u64> tot(n_a);
-    {
-      D2H back(ctx);
-      HIP_TRY(back.add(tot.data(), dtot.p, uint64_t(n_a) * 8));
-      HIP_TRY(back.finish());
-    }
-    std::vector<uint32_t> order;
-    order.reserve(n_a);
-    for (uint32_t i = 0; i < n_a; ++i)
-      if (tot[i]) order.push_back(i);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return tot[x] > tot[y]; });
-    const uint32_t want = k ? std::min<uint32_t>(k, uint32_t(order.size())) : uint32_t(order.size());
-    *out_n = want;
-    if (want > cap) return fail(FBK_E_CAPACITY, "topk: " + std::to_string(want) + " results, buffers hold " + std::to_string(cap));
-    for (uint32_t j = 0; j < want; ++j) {
-      out_index[j] = order[j];
-      out_count[j] = tot[order[j]];
-    }
-    return FBK_OK;
-  }
-  HIP_TRY(dsk.alloc(ctx, uint64_t(n_a) * 8));
-  HIP_TRY(dval.alloc(ctx, uint64_t(n_a) * 4));
-  HIP_TRY(dsv.alloc(ctx, uint64_t(n_a) * 4));
-  HIP_TRY(dnz.alloc(ctx, 16));
-  hipLaunchKernelGGL(fbk::k_iota_u32, dim3((n_a + 255) / 256), dim3(256), 0, ctx->stream, dval.as<uint32_t>(), n_a);
-  size_t tb = 0;
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, dtot.as<u64>(), dsk.as<u64>(), dval.as<uint32_t>(), dsv.as<uint32_t>(),
-                                                       int(n_a), 0, 64, ctx->stream));
-  HIP_TRY(dtmp.alloc(ctx, std::max<size_t>(tb, 16)));
-  HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(dtmp.p, tb, dtot.as<u64>(), dsk.as<u64>(), dval.as<uint32_t>(), dsv.as<uint32_t>(),
-                                                       int(n_a), 0, 64, ctx->stream));
-  hipLaunchKernelGGL(fbk::k_count_nonzero_desc, dim3(1), dim3(1), 0, ctx->stream, dsk.as<u64>(), n_a, dnz.as<uint32_t>());
-  HIP_TRY(hipGetLastError());
-  uint32_t nz = 0;
-  HIP_TRY(hipMemcpyAsync(&nz, dnz.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  const uint32_t want = k ? std::min(k, nz) : nz;  // rows without a single common column are not results
-  *out_n = want;
-  if (want > cap) return fail(FBK_E_CAPACITY, "topk: " + std::to_string(want) + " results, buffers hold " + std::to_string(cap));
-  if (want) {
-    D2H back(ctx);
-    HIP_TRY(back.add(out_index, dsv.p, uint64_t(want) * 4));
-    HIP_TRY(back.add(out_count, dsk.p, uint64_t(want) * 8));
-    HIP_TRY(back.finish());
-  }
-  return FBK_OK;
-}
-
-
-int32_t topn_impl(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* filter, const uint32_t* rows_f,
-                  uint32_t n_shards, uint32_t k, uint64_t min_threshold, uint64_t tanimoto_threshold, uint32_t* out_index, uint64_t* out_count,
-                  uint32_t cap, uint32_t* out_n, bool reference_operator = false) {
-  if (!ctx || !a || !out_n || (n_shards && n_a && !rows_a) || (filter && n_shards && !rows_f) || (cap && (!out_index || !out_count)))
-    return fail(FBK_E_INVALID, "NULL argument");
-  if (n_a > (1u << 22)) return fail(FBK_E_INVALID, "topk: at most 2^22 rows");
-  if (tanimoto_threshold > 100) return fail(FBK_E_INVALID, "topn: Tanimoto threshold is a percentage (0..100)");
-  *out_n = 0;
-  if (n_shards == 0 || n_a == 0) return FBK_OK;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  DevBuf dtot, dcand;
-  HIP_TRY(dtot.alloc(ctx, uint64_t(n_a) * 8));
-  const uint32_t cand_n = topn_cand_n(ctx, k, n_a, reference_operator);
-  if (cand_n) HIP_TRY(dcand.alloc(ctx, uint64_t(n_a) * 8));
-  if (int32_t rc = topn_totals_locked(ctx, a, rows_a, n_a, filter, rows_f, n_shards, min_threshold, tanimoto_threshold, dtot.as<u64>(), cand_n, dcand.as<u64>())) return rc;
-  if (cand_n) hipLaunchKernelGGL(fbk::k_topn_mask, dim3((n_a + 255) / 256), dim3(256), 0, ctx->stream, dtot.as<u64>(), dcand.as<u64>(), n_a);
-  HIP_TRY(hipGetLastError());
-  return topn_order_locked(ctx, dtot, n_a, k, out_index, out_count, cap, out_n);
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t fbk_topk(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* filter,
-                 const uint32_t* rows_f, uint32_t n_shards, uint32_t k, uint32_t* out_index, uint64_t* out_count, uint32_t cap,
-                 uint32_t* out_n) try {
-  FBK_ENTER(ctx);
-  return topn_impl(ctx, a, rows_a, n_a, filter, rows_f, n_shards, k, 0, 0, out_index, out_count, cap, out_n);
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_topn(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* filter,
-                 const uint32_t* rows_f, uint32_t n_shards, uint32_t n, uint64_t min_threshold, uint64_t tanimoto_threshold,
-                 uint32_t* out_index, uint64_t* out_count, uint32_t cap, uint32_t* out_n) try {
-  FBK_ENTER(ctx);
-  return topn_impl(ctx, a, rows_a, n_a, filter, rows_f, n_shards, n, min_threshold, tanimoto_threshold, out_index, out_count, cap, out_n, /*reference_operator=*/true);
-} FBK_ABI_CATCH(ctx)
-
 int32_t fbk_batch_compact(fbk_ctx* ctx, fbk_batch* batch, uint64_t* out_arena_bytes) try {
   FBK_ENTER(ctx);
   if (!batch) return fail(FBK_E_INVALID, "batch is NULL");
@@ -926,73 +723,6 @@ int32_t fbk_batch_memory(fbk_ctx* ctx, const fbk_batch* batch, uint64_t* out_are
   if (out_arena_bytes) *out_arena_bytes = batch->arena_bytes;
   if (out_shadow_bytes) *out_shadow_bytes = batch->shadow_bytes;
   if (out_shadow_state) *out_shadow_state = batch->shadow_state;
-  return FBK_OK;
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_topn_partials(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* filter, const uint32_t* rows_f,
-                          uint32_t n_shards, uint32_t n, uint64_t min_threshold, uint64_t tanimoto_threshold, uint64_t* out_totals, uint64_t* out_candidates) try {
-  FBK_ENTER(ctx);
-  if (!ctx || !out_totals || !out_candidates || (n_shards && n_a && (!a || !rows_a)) || (filter && n_shards && !rows_f)) return fail(FBK_E_INVALID, "NULL argument");
-  if (n_a > (1u << 22)) return fail(FBK_E_INVALID, "topk: at most 2^22 rows");
-  if (tanimoto_threshold > 100) return fail(FBK_E_INVALID, "topn: Tanimoto threshold is a percentage (0..100)");
-  std::memset(out_totals, 0, uint64_t(n_a) * 8);
-  std::memset(out_candidates, 0, uint64_t(n_a) * 8);
-  if (n_shards == 0 || n_a == 0) return FBK_OK;  // a member without shards: zeros, no candidates
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  DevBuf dtc;  // [totals | candidates]
-  HIP_TRY(dtc.alloc(ctx, uint64_t(n_a) * 16));
-  const uint32_t cand_n = topn_cand_n(ctx, n, n_a, true);
-  u64* d_cand = dtc.as<u64>() + n_a;
-  if (int32_t rc = topn_totals_locked(ctx, a, rows_a, n_a, filter, rows_f, n_shards, min_threshold, tanimoto_threshold, dtc.as<u64>(), cand_n, d_cand)) return rc;
-  HIP_TRY(hipGetLastError());
-  D2H back(ctx);
-  HIP_TRY(back.add(out_totals, dtc.p, uint64_t(n_a) * 8));
-  if (cand_n) HIP_TRY(back.add(out_candidates, d_cand, uint64_t(n_a) * 8));
-  HIP_TRY(back.finish());
-  if (!cand_n)  // no candidate pass: every row that has a total is its own candidate
-    for (uint32_t i = 0; i < n_a; ++i) out_candidates[i] = out_totals[i] ? 1 : 0;
-  return FBK_OK;
-} FBK_ABI_CATCH(ctx)
-
-int32_t fbk_topk_bsi(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* filter,
-                     const uint32_t* rows_f, uint32_t n_shards, uint32_t flags, fbk_batch** out_batch, uint32_t* out_depth) try {
-  FBK_ENTER(ctx);
-  if (!ctx || !a || !out_batch || !out_depth || (n_shards && n_a && !rows_a) || (filter && n_shards && !rows_f))
-    return fail(FBK_E_INVALID, "NULL argument");
-  if (flags & ~FBK_SETOP_OPTIMIZE) return fail(FBK_E_INVALID, "unknown flags");
-  if (n_a > (1u << 20)) return fail(FBK_E_INVALID, "topk_bsi: at most 2^20 rows (one shard width of row ids per output row)");
-  *out_batch = nullptr;
-  *out_depth = 0;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  DevBuf dtot, dmax;
-  HIP_TRY(dtot.alloc(ctx, std::max<uint64_t>(n_a, 1) * 8));
-  HIP_TRY(dmax.alloc(ctx, 8));
-  HIP_TRY(hipMemsetAsync(dmax.p, 0, 8, ctx->stream));
-  u64 mx = 0;
-  if (n_shards && n_a) {
-    if (int32_t rc = topn_totals_locked(ctx, a, rows_a, n_a, filter, rows_f, n_shards, 0, 0, dtot.as<u64>())) return rc;
-    hipLaunchKernelGGL(fbk::k_max_u64, dim3(std::min<uint32_t>(1024, (n_a + 255) / 256)), dim3(256), 0, ctx->stream, dtot.as<u64>(), uint64_t(n_a),
-                       dmax.as<u64>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&mx, dmax.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-  }
-  const uint32_t depth = uint32_t(bits_len64(mx));  // planes the largest count needs (bsiBuilder grows the same way, bsi.go:256)
-  *out_depth = depth;
-  CellOutput out;
-  if (int32_t rc = out.alloc(ctx, depth, 0, "topk_bsi")) return rc;
-  if (depth) {
-    fbk_batch* o = out.batch();
-    const uint64_t n_slots = uint64_t(depth) * fbk::kSlots;
-    HIP_TRY(hipMemsetAsync(o->d_arena, 0, n_slots * 8192ull, ctx->stream));
-    hipLaunchKernelGGL(fbk::k_counts_to_bsi, dim3((n_a + 255) / 256), dim3(256), 0, ctx->stream, dtot.as<u64>(), n_a, depth, o->d_arena);
-    hipLaunchKernelGGL(fbk::k_cell_stats, dim3(uint32_t((n_slots + 3) / 4)), dim3(256), 0, ctx->stream, o->d_arena, o->d_slots, out.runs(), n_slots);
-    if (int32_t rc = out.finish(flags, 0, nullptr)) return rc;
-  }
-  (void)hipStreamSynchronize(ctx->stream);
-  *out_batch = out.release();
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 
