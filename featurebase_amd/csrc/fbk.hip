@@ -38,6 +38,7 @@
 #include "fbk_distinct_rows.hip.h"
 #include "fbk_expr.hip.h"
 #include "fbk_expr_topk.hip.h"
+#include "fbk_group_select.hip.h"
 #include "fbk_wire_kernels.hip.h"
 
 using fbk::Slot;
@@ -1393,6 +1394,7 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_query_api.inc"
 #include "fbk_matrix_sum_api.inc"
 #include "fbk_count_cube_api.inc"
+#include "fbk_group_select_api.inc"
 #include "fbk_matrix_distinct_api.inc"
 #include "fbk_extract_api.inc"
 #include "fbk_sort_api.inc"

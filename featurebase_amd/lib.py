@@ -21,6 +21,10 @@ SORT_DESC, SORT_KEEP_ZERO = 1, 2
 RANK_FROM_TOP = 1 << 63
 SETOP_KEEP_BITMAP, SETOP_OPTIMIZE = 0, 1
 QUERY_ACCUMULATE = 1
+GROUPSEL_DEVICE, GROUPSEL_HOST = 1, 2
+GROUPSEL_NONE, GROUPSEL_COUNT, GROUPSEL_AGG = 0, 1, 2
+HAVING_EQ, HAVING_NEQ, HAVING_LT, HAVING_LTE, HAVING_GT, HAVING_GTE = 1, 2, 3, 4, 5, 6
+HAVING_BETWEEN, HAVING_BTWN_LT_LTE, HAVING_BTWN_LTE_LT, HAVING_BTWN_LT_LT = 7, 8, 9, 10
 
 
 class FbkError(RuntimeError):
@@ -55,6 +59,28 @@ class MatrixArgs(C.Structure):
         ("rows_f", C.c_void_p),
         ("n_shards", C.c_uint32),
         ("pad", C.c_uint32),
+    ]
+
+
+class GroupbyTerm(C.Structure):
+    """Mirror of fbk_groupby_term (include/fbk.h): one sort term of a GroupBy selection."""
+
+    _fields_ = [("subject", C.c_uint32), ("desc", C.c_uint32)]
+
+
+class GroupbySelect(C.Structure):
+    """Mirror of fbk_groupby_select (include/fbk.h): having / sort / offset / limit of a GroupBy, 64 bytes."""
+
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("n_sort", C.c_uint32),
+        ("sort", GroupbyTerm * 2),
+        ("having_subject", C.c_uint32),
+        ("having_op", C.c_uint32),
+        ("having_lo", C.c_int64),
+        ("having_hi", C.c_int64),
+        ("offset", C.c_uint64),
+        ("limit", C.c_uint64),
     ]
 
 
@@ -150,6 +176,10 @@ SIGNATURES = {
     "fbk_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "fbk_query_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_count_matrix_distinct": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "fbk_count_matrix_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),
+    "fbk_count_cube_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),
+    "fbk_count_matrix_sum_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),
+    "fbk_select_groups": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),
     "fbk_extract_open": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vpp, _u64p]),
     "fbk_extract_span": (C.c_int32, [_vp, _vp, _u32p, _u32p]),
     "fbk_extract_columns": (C.c_int32, [_vp, _vp, _vp]),

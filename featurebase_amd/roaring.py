@@ -366,6 +366,88 @@ def compile_expr(tree) -> Tuple[List[ExprLeaf], np.ndarray]:
     return leaves, np.asarray(prog, dtype=np.uint32)
 
 
+class GroupSelect:
+    """having / sort / offset / limit of a GroupBy (fbk_groupby_select, include/fbk.h).
+    sort: a reference-style string ("count desc, sum asc": getSorter, executor.go:3130-3162) or a list of (subject, desc) pairs;
+    a term whose subject already occurred is dropped (it can never decide).  having: a reference-style condition string
+    ("count > 5", "-5 < sum < 27", "sum >< [1, 9]") or (subject, op, lo[, hi]) with op one of OPS.  path: None, "device" or "host"."""
+
+    SUBJECTS = {"count": L.GROUPSEL_COUNT, "sum": L.GROUPSEL_AGG, "aggregate": L.GROUPSEL_AGG}
+    OPS = {"==": L.HAVING_EQ, "!=": L.HAVING_NEQ, "<": L.HAVING_LT, "<=": L.HAVING_LTE, ">": L.HAVING_GT, ">=": L.HAVING_GTE, "><": L.HAVING_BETWEEN,
+           "<x<=": L.HAVING_BTWN_LT_LTE, "<=x<": L.HAVING_BTWN_LTE_LT, "<x<": L.HAVING_BTWN_LT_LT, "<=x<=": L.HAVING_BETWEEN}
+
+    @staticmethod
+    def parse_sort(spec: str) -> List[Tuple[int, bool]]:
+        """getSorter's rules: terms split on commas, `count` | `sum` | `aggregate`, then `asc` | `desc` (default desc).  Raises
+        ValueError with the reference's message."""
+        terms = []
+        for term in spec.split(","):
+            term = term.strip()
+            parts = term.split()
+            if not parts:
+                raise ValueError(f"invalid sorting directive: '{term}'")
+            if parts[0] not in GroupSelect.SUBJECTS:
+                raise ValueError(f"sorting is only supported on count, aggregate, or sum, not '{parts[0]}'")
+            if len(parts) == 1:
+                desc = True
+            elif len(parts) > 2:
+                raise ValueError(f"parsing sort directive: '{term}': too many elements")
+            elif parts[1] in ("asc", "desc"):
+                desc = parts[1] == "desc"
+            else:
+                raise ValueError(f"unknown sort direction '{parts[1]}'")
+            terms.append((GroupSelect.SUBJECTS[parts[0]], desc))
+        return terms
+
+    @staticmethod
+    def parse_condition(text: str) -> Tuple[int, int, int, int]:
+        """Condition(count|sum <op> v), Condition(lo < sum <= hi), Condition(sum >< [lo, hi]) -> (subject, op, lo, hi)"""
+        import re
+
+        num, subj = r"(-?\d+)", r"(count|sum)"
+        t = text.strip()
+        m = re.fullmatch(rf"{num}\s*(<=?)\s*{subj}\s*(<=?)\s*{num}", t)
+        if m:
+            return GroupSelect.SUBJECTS[m.group(3)], GroupSelect.OPS[f"{m.group(2)}x{m.group(4)}"], int(m.group(1)), int(m.group(5))
+        m = re.fullmatch(rf"{subj}\s*><\s*\[\s*{num}\s*,\s*{num}\s*\]", t)
+        if m:
+            return GroupSelect.SUBJECTS[m.group(1)], L.HAVING_BETWEEN, int(m.group(2)), int(m.group(3))
+        m = re.fullmatch(rf"{subj}\s*(==|!=|<=|>=|<|>)\s*{num}", t)
+        if m:
+            return GroupSelect.SUBJECTS[m.group(1)], GroupSelect.OPS[m.group(2)], int(m.group(3)), 0
+        raise ValueError(f"Condition() only supports count or sum against integers: '{text}'")
+
+    def __init__(self, sort=None, having=None, offset: int = 0, limit: Optional[int] = None, path: Optional[str] = None):
+        terms = self.parse_sort(sort) if isinstance(sort, str) else [(self.SUBJECTS.get(s, s), bool(d)) for s, d in (sort or [])]
+        self.sort = []
+        for s, d in terms:
+            if all(s != s0 for s0, _ in self.sort):
+                self.sort.append((s, d))
+        if isinstance(having, str):
+            having = self.parse_condition(having)
+        elif having is not None:
+            subject, op, lo = having[0], having[1], having[2]
+            having = (self.SUBJECTS.get(subject, subject), self.OPS.get(op, op), int(lo), int(having[3]) if len(having) > 3 else 0)
+        if having is not None and having[0] == L.GROUPSEL_COUNT:
+            two = having[1] >= L.HAVING_BETWEEN
+            if having[2] < 0 or (two and having[3] < 0):
+                having = (L.GROUPSEL_COUNT, L.HAVING_BETWEEN, 1, 0)  # a negative literal in a count condition matches nothing (executor.go:3792-3795)
+        self.having, self.offset, self.limit = having, int(offset), limit
+        self.flags = {None: 0, "device": L.GROUPSEL_DEVICE, "host": L.GROUPSEL_HOST}[path]
+
+    def struct(self) -> "L.GroupbySelect":
+        s = L.GroupbySelect()
+        s.flags, s.n_sort = self.flags, len(self.sort)
+        for t, (subject, desc) in enumerate(self.sort[:2]):
+            s.sort[t].subject, s.sort[t].desc = subject, int(desc)
+        if self.having is not None:
+            s.having_subject, s.having_op = self.having[0], self.having[1]
+            wrap = lambda v: v - (1 << 64) if v >= (1 << 63) else v  # (a count bound is read as uint64)
+            s.having_lo, s.having_hi = wrap(self.having[2]), wrap(self.having[3])
+        s.offset, s.limit = self.offset, (1 << 64) - 1 if self.limit is None else self.limit
+        return s
+
+
 class Context:
     """One GPU.  Fails loudly when libfbk.so is missing or no gfx950 device is visible."""
 
@@ -872,6 +954,67 @@ class Context:
         L.check(self.lib.fbk_count_matrix_distinct(*args, bit_depth, n_shards, distinct.ctypes.data, counts.ctypes.data))
         del keep
         return distinct, counts
+
+    # -- GroupBy having / sort / offset / limit ---------------------------------------------------
+    def _select(self, call, args, sel, has_agg: bool, cap: Optional[int], aggs_slot: bool = True):
+        """`call`(*args, sel, out_cells, out_counts[, out_aggs], cap, out_n, out_matched), one retry with the reported size when
+        `cap` records were too few (as bsi_sort).  aggs_slot: the call has an out_aggs argument even when has_agg is false (NULL then)."""
+        st = sel.struct() if isinstance(sel, GroupSelect) else sel
+        if cap is None:
+            cap = 1 << 16 if st.limit == (1 << 64) - 1 else min(int(st.limit), 1 << 24)
+        n, matched = C.c_uint64(), C.c_uint64()
+        for _ in range(2):
+            cells, counts = np.zeros(max(cap, 1), dtype=np.uint32), np.zeros(max(cap, 1), dtype=np.uint64)
+            aggs = np.zeros(max(cap, 1), dtype=np.int64) if has_agg else None
+            outs = (cells.ctypes.data, counts.ctypes.data) + ((aggs.ctypes.data,) if has_agg else (None,) if aggs_slot else ())
+            rc = call(*args, C.byref(st), *outs, cap, C.byref(n), C.byref(matched))
+            if rc != L.FBK_E_CAPACITY:
+                break
+            cap = int(n.value)
+        L.check(rc)
+        k = int(n.value)
+        if has_agg:
+            return cells[:k].copy(), counts[:k].copy(), aggs[:k].copy(), int(matched.value)
+        return cells[:k].copy(), counts[:k].copy(), int(matched.value)
+
+    def count_matrix_select(self, a: Batch, rows_a, b: Batch, rows_b, sel, filt: Optional[Batch] = None, rows_f=None, cap: Optional[int] = None):
+        """count_matrix's groups through having / sort / offset / limit on the device (fbk_count_matrix_select): (cells uint32 —
+        cell = i * n_b + j —, counts uint64, matched = the groups before offset / limit).  sel: a GroupSelect."""
+        ra, rb = np.ascontiguousarray(rows_a, dtype=np.uint32), np.ascontiguousarray(rows_b, dtype=np.uint32)
+        n_shards, n_a = ra.shape
+        assert rb.shape[0] == n_shards
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        args = (self.h, a.h, ra.ctypes.data, n_a, b.h, rb.ctypes.data, rb.shape[1], filt.h if filt is not None else None,
+                rf.ctypes.data if rf is not None else None, n_shards)
+        return self._select(self.lib.fbk_count_matrix_select, args, sel, False, cap, aggs_slot=False)
+
+    def count_cube_select(self, p: Batch, rows_p, a: Batch, rows_a, b: Batch, rows_b, sel, filt: Optional[Batch] = None, rows_f=None, cap: Optional[int] = None):
+        """count_cube's groups through having / sort / offset / limit on the device (fbk_count_cube_select): (cells uint32 —
+        cell = (p * n_a + i) * n_b + j —, counts uint64, matched)."""
+        rp, ra, rb = (np.ascontiguousarray(r, dtype=np.uint32) for r in (rows_p, rows_a, rows_b))
+        n_shards, n_p = rp.shape
+        assert ra.ndim == 2 and rb.ndim == 2 and ra.shape[0] == n_shards and rb.shape[0] == n_shards
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        args = (self.h, p.h, rp.ctypes.data, n_p, a.h, ra.ctypes.data, ra.shape[1], b.h, rb.ctypes.data, rb.shape[1],
+                filt.h if filt is not None else None, rf.ctypes.data if rf is not None else None, n_shards)
+        return self._select(self.lib.fbk_count_cube_select, args, sel, False, cap, aggs_slot=False)
+
+    def count_matrix_sum_select(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, bit_depth: int, sel,
+                                filt: Optional[Batch] = None, rows_f=None, cap: Optional[int] = None):
+        """count_matrix_sum's groups through having / sort / offset / limit on the device (fbk_count_matrix_sum_select): (cells
+        uint32, counts uint64, sums int64 — Base not added —, matched)."""
+        args, keep, n_shards, n_a, n_b = self._msum_args(a, rows_a, b, rows_b, bsi, base_rows, filt, rows_f)
+        out = self._select(self.lib.fbk_count_matrix_sum_select, args + (bit_depth, n_shards), sel, True, cap)
+        del keep
+        return out
+
+    def select_groups(self, counts, aggs, sel, cap: Optional[int] = None):
+        """The selection stage alone over host arrays counts [n] and aggs [n] or None (fbk_select_groups): (cells, counts[, aggs],
+        matched) — aggs only when given."""
+        c = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        g = np.ascontiguousarray(aggs, dtype=np.int64).reshape(-1) if aggs is not None else None
+        assert g is None or g.size == c.size
+        return self._select(self.lib.fbk_select_groups, (self.h, c.ctypes.data, g.ctypes.data if g is not None else None, c.size), sel, g is not None, cap)
 
     # -- prepared (launch-only) forms of the query-level calls -------------------------------
     def prepare_count_matrix(self, a: Batch, rows_a, b: Batch, rows_b, filt: Optional[Batch] = None, rows_f=None, keep_per_shard: bool = False) -> Query:

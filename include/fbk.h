@@ -58,7 +58,8 @@ extern "C" {
  *   6 (round 6): + fbk_comm_unique_id / fbk_comm_init / fbk_comm_all_reduce_u64 / fbk_comm_fence / fbk_comm_close (the
  *      one-process-per-GPU exchange issued by the library itself).  fbk_batch_compact refuses a batch of another context;
  *      fbk_group_topn refuses members whose topn_semantics differ.  Later, entry points added at the same version:
- *      fbk_count_matrix_distinct; fbk_extract_open / _span / _columns / _bsi / _rows / _free; fbk_bsi_sort;
+ *      fbk_count_matrix_distinct; fbk_count_matrix_select / fbk_count_cube_select / fbk_count_matrix_sum_select / fbk_select_groups;
+ *      fbk_extract_open / _span / _columns / _bsi / _rows / _free; fbk_bsi_sort;
  *      fbk_extract_open_columns; fbk_bsi_quantiles; fbk_bsi_percentile; fbk_bsi_distinct_rows;
  *      fbk_expr_count / fbk_expr_eval / fbk_query_expr; fbk_expr_bsi_agg / fbk_query_expr_bsi; fbk_expr_row_counts / fbk_expr_topk /
  *      fbk_expr_topn.
@@ -592,6 +593,96 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
                                   const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
                                   const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
                                   uint64_t* out_distinct, uint64_t* out_counts);
+
+/* ---- GroupBy(..., having=, sort=, offset=, limit=): only the selected groups leave the device -----
+ * executeGroupBy's tail (executor.go:3176-3459: ApplyConditionToGroupCounts / satisfiesCondition :3787-3916, groupCountSorter and
+ * getSorter :3096-3162, sort.Stable :3409, applyLimitAndOffsetToGroupByResult :3441-3459) applied to the totals of a GroupBy call
+ * while they are still on the device.  Over cells 0 .. n-1 (the full call's output index: odometer order, last field fastest) with
+ * counts[cell] (uint64) and, where the call has an aggregate, aggs[cell] (int64):
+ *  - Groups: the cells with count > 0 (:8913) that pass `having`; *out_matched = their number, before offset / limit.
+ *  - having_subject FBK_GROUPSEL_NONE: no condition.  _COUNT compares the count as uint64 (having_lo / having_hi are read as uint64),
+ *    _AGG compares the aggregate as int64.  having_op: FBK_HAVING_EQ, _NEQ, _LT, _LTE, _GT, _GTE compare x with having_lo
+ *    (having_hi is ignored); _BETWEEN lo <= x <= hi, _BTWN_LT_LTE lo < x <= hi, _BTWN_LTE_LT lo <= x < hi, _BTWN_LT_LT lo < x < hi;
+ *    lo > hi selects nothing.  (The reference's "a negative literal in a count condition matches nothing" — Uint64Value fails,
+ *    :3792-3795 — is the CALLER's rule: this struct cannot express a negative count bound.)
+ *  - sort: n_sort = 0, 1 or 2 terms {subject FBK_GROUPSEL_COUNT | _AGG, desc 0 | 1}, compared in the order given; groups equal in
+ *    every term keep ascending cell order (sort.Stable over the odometer order).  n_sort = 0: ascending cell order.  The same
+ *    subject twice is FBK_E_INVALID (a repeated term never decides: drop it before the call).
+ *  - offset, then limit, on that list: the records of ranks [offset, offset + limit).  limit = UINT64_MAX: none; offset + limit may
+ *    exceed 2^64; offset >= *out_matched gives *out_n = 0.  (applyLimitAndOffsetToGroupByResult IGNORES such an offset, and a
+ *    GroupBy with neither sort nor having applies its limit twice, :3302 and :3331: both are the caller's to reproduce —
+ *    fbk::Executor::GroupBy does — and *out_matched is what tells it.)
+ *  - Output: record k = {out_cells[k] (uint32), out_counts[k], out_aggs[k]}.  *out_n = the records of the result and *out_matched
+ *    are always written, on FBK_OK and on FBK_E_CAPACITY; cap < *out_n -> FBK_E_CAPACITY, the arrays untouched (the fbk_bsi_sort
+ *    convention).  cap > 0 with a NULL array is FBK_E_INVALID.
+ *  - flags: FBK_GROUPSEL_DEVICE / FBK_GROUPSEL_HOST pin the path (tests, measurements); both is FBK_E_INVALID; neither: the library
+ *    downloads the totals and selects on the host when n <= 2^16 cells (measured: the device stage costs about 45 us of launches
+ *    without a sort and about 200 us with one, which the transfer of 2^16 cells and the host's pass still undercut or match;
+ *    docs/history/DESIGN_groupby_select_measurements.md), on the device above.  Both paths give identical output.
+ *  - An unknown flag, op, subject or desc, n_sort > 2, a sort term or a having on _AGG where the call has no aggregate: FBK_E_INVALID,
+ *    checked with the GroupBy call's own argument checks before any launch.  Every error leaves the context usable.
+ *  - Device path: one ordered compaction pass over the cells (wave ballot ranks, block counts, a scan, an emit pass) gives the
+ *    matched cells in ascending order; without a sort only the ranks [offset, offset + limit) are written.  With a sort and
+ *    K = offset + limit < matched, an MSB-first radix select (8 bits per pass over the order-preserving 64-bit keys of the terms,
+ *    digits chosen on the device) finds the key of rank K, a second ordered pass keeps the keys below it and the first ties in cell
+ *    order, and only those K are sorted (stable radix sort, secondary term first).  Without an effective limit all matched groups
+ *    are sorted.  Device scratch beside the totals themselves (8 n bytes, 16 n with an aggregate), with U = ceil(n / 512),
+ *    K = min(offset + limit, matched), W = the cells that are sorted (K if K < matched, else matched) and n_out the records:
+ *      16 (U + 1) + the scan's temporary storage (~U) + 20 n_out, and with a sort 4 * matched + 20 W + the radix sort's
+ *      temporary storage (~12 W) + (K < matched: 4 K + 2^10 + 32) bytes: never a (key, key, index) record per cell.
+ *
+ * fbk_count_matrix_select: fbk_count_matrix's arguments (no per-shard output) — the one- and two-field GroupBy on counts
+ *   (n_b == 1 with B = the filter row is the one-field form); cell = i * n_b + j.  Counts only.
+ * fbk_count_cube_select: fbk_count_cube's arguments; cell = (p * n_a + i) * n_b + j.  Counts only.
+ * fbk_count_matrix_sum_select: fbk_count_matrix_sum's arguments; the aggregate is the sum (Base NOT added), the count is the sum's
+ *   count (over exists).
+ * fbk_select_groups: the stage alone over host arrays counts[n], aggs[n] (aggs may be NULL: counts only), n <= 2^24: for
+ *   fbk_count_matrix_distinct results and results merged from several blocked calls.
+ * n_shards == 0 or zero cells: *out_n = *out_matched = 0, FBK_OK. */
+#define FBK_GROUPSEL_DEVICE 1u
+#define FBK_GROUPSEL_HOST 2u
+#define FBK_GROUPSEL_NONE 0u
+#define FBK_GROUPSEL_COUNT 1u
+#define FBK_GROUPSEL_AGG 2u
+#define FBK_HAVING_EQ 1u
+#define FBK_HAVING_NEQ 2u
+#define FBK_HAVING_LT 3u
+#define FBK_HAVING_LTE 4u
+#define FBK_HAVING_GT 5u
+#define FBK_HAVING_GTE 6u
+#define FBK_HAVING_BETWEEN 7u
+#define FBK_HAVING_BTWN_LT_LTE 8u
+#define FBK_HAVING_BTWN_LTE_LT 9u
+#define FBK_HAVING_BTWN_LT_LT 10u
+typedef struct fbk_groupby_term {
+  uint32_t subject; /* FBK_GROUPSEL_COUNT | FBK_GROUPSEL_AGG */
+  uint32_t desc;    /* 0 ascending, 1 descending */
+} fbk_groupby_term;
+typedef struct fbk_groupby_select {
+  uint32_t flags;
+  uint32_t n_sort;
+  fbk_groupby_term sort[2];
+  uint32_t having_subject; /* FBK_GROUPSEL_NONE | _COUNT | _AGG */
+  uint32_t having_op;      /* FBK_HAVING_* */
+  int64_t having_lo, having_hi;
+  uint64_t offset, limit;
+} fbk_groupby_select; /* 64 bytes */
+int32_t fbk_count_matrix_select(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
+                                const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
+                                uint32_t n_shards, const fbk_groupby_select* sel, uint32_t* out_cells, uint64_t* out_counts,
+                                uint64_t cap, uint64_t* out_n, uint64_t* out_matched);
+int32_t fbk_count_cube_select(fbk_ctx* ctx, const fbk_batch* p, const uint32_t* rows_p, uint32_t n_p, const fbk_batch* a,
+                              const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b, const uint32_t* rows_b, uint32_t n_b,
+                              const fbk_batch* filter, const uint32_t* rows_f, uint32_t n_shards, const fbk_groupby_select* sel,
+                              uint32_t* out_cells, uint64_t* out_counts, uint64_t cap, uint64_t* out_n, uint64_t* out_matched);
+int32_t fbk_count_matrix_sum_select(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
+                                    const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
+                                    const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
+                                    const fbk_groupby_select* sel, uint32_t* out_cells, uint64_t* out_counts, int64_t* out_aggs,
+                                    uint64_t cap, uint64_t* out_n, uint64_t* out_matched);
+int32_t fbk_select_groups(fbk_ctx* ctx, const uint64_t* counts, const int64_t* aggs, uint64_t n, const fbk_groupby_select* sel,
+                          uint32_t* out_cells, uint64_t* out_counts, int64_t* out_aggs, uint64_t cap, uint64_t* out_n,
+                          uint64_t* out_matched);
 
 /* ---- Extract(filter, Rows(f1), Rows(f2), ...): the records of a column filter -------------------
  * executeExtract (executor.go:4711-5046), usually under executeLimitCall's Extract(Limit(filter, limit=, offset=), ...)

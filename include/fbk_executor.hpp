@@ -27,6 +27,7 @@
 #include <string>
 #include <vector>
 
+#include "../featurebase_amd/csrc/fbk_group_select_plan.h"  // the host rules of GroupBy's having / sort / offset / limit
 #include "fbk_roaring.hpp"
 
 namespace fbk {
@@ -46,6 +47,49 @@ struct GroupCount {  // executor.go GroupCount
   int64_t Agg = 0;
   bool operator==(const GroupCount& o) const { return Group == o.Group && Count == o.Count && Agg == o.Agg; }
 };
+struct GroupByCondition {  // having=Condition(count|sum <op> v): satisfiesCondition (executor.go:3787-3901)
+  std::string subject;    // "count" | "sum"
+  uint32_t op = 0;        // FBK_HAVING_*
+  int64_t lo = 0, hi = 0;  // hi: the BETWEEN forms only
+};
+struct GroupByOptions {  // GroupBy(..., having=, sort=, offset=, limit=) (executor.go:3176-3459)
+  std::optional<GroupByCondition> having;
+  std::string sort;  // getSorter's string ("count desc, sum asc"); empty: no sort
+  std::optional<uint64_t> offset, limit;
+};
+// getSorter (executor.go:3130-3162): terms split on commas, `count` | `sum` | `aggregate`, then `asc` | `desc` (default desc)
+inline std::vector<fbk_groupby_term> ParseGroupBySort(const std::string& spec) {
+  std::vector<fbk_groupby_term> out;
+  size_t at = 0;
+  for (;;) {
+    const size_t comma = spec.find(',', at);
+    std::string term = spec.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+    const size_t b = term.find_first_not_of(" \t\n\r"), e = term.find_last_not_of(" \t\n\r");
+    term = b == std::string::npos ? "" : term.substr(b, e - b + 1);
+    std::vector<std::string> parts;
+    for (size_t i = 0; i < term.size();) {
+      const size_t w = term.find_first_not_of(" \t\n\r", i);
+      if (w == std::string::npos) break;
+      const size_t we = term.find_first_of(" \t\n\r", w);
+      parts.push_back(term.substr(w, we == std::string::npos ? std::string::npos : we - w));
+      i = we == std::string::npos ? term.size() : we;
+    }
+    fbk_groupby_term t{FBK_GROUPSEL_COUNT, 1};
+    if (parts.empty()) throw Error(FBK_E_INVALID, "invalid sorting directive: '" + term + "'");
+    if (parts[0] == "count") t.subject = FBK_GROUPSEL_COUNT;
+    else if (parts[0] == "aggregate" || parts[0] == "sum") t.subject = FBK_GROUPSEL_AGG;
+    else throw Error(FBK_E_INVALID, "sorting is only supported on count, aggregate, or sum, not '" + parts[0] + "'");
+    if (parts.size() > 2) throw Error(FBK_E_INVALID, "parsing sort directive: '" + term + "': too many elements");
+    if (parts.size() == 2) {
+      if (parts[1] == "asc") t.desc = 0;
+      else if (parts[1] != "desc") throw Error(FBK_E_INVALID, "unknown sort direction '" + parts[1] + "'");
+    }
+    out.push_back(t);
+    if (comma == std::string::npos) break;
+    at = comma + 1;
+  }
+  return out;
+}
 struct ValCount {  // executor.go:8380; integer fields only
   int64_t Val = 0, Count = 0;
   ValCount Add(const ValCount& o) const { return {Val + o.Val, Count + o.Count}; }  // :8438
@@ -708,6 +752,132 @@ class Executor {
     GroupAgg agg;
     agg.sum_field = agg_field;
     group_by_rec(fields, 0, prefix.get(), agg, limit, group, out);
+    return out;
+  }
+
+  // GroupBy(..., having=Condition(...), sort="...", offset=, limit=) (executeGroupBy, executor.go:3176-3459).  When the whole GroupBy
+  // fits ONE library call — one to three fields of at most kSumBlock rows within the cube's 2^24 groups, or aggregate=Sum over one
+  // or two fields whose Base is 0 (the call's aggregate is the sum without Base) — the matching fbk_*_select call selects on the
+  // device and only the winners come back; otherwise today's blocked path runs and fbk_group_select::select picks on the host.
+  // Two quirks of the reference are reproduced HERE (the C ABI has neither): with neither sort nor having the limit is applied
+  // while merging and then offset and limit again (:3302, :3331: limit=L, offset=O yields the groups O .. L-1), and an offset >=
+  // the number of results is ignored (:3446).  A negative literal in a count condition matches nothing (:3792-3795).
+  std::vector<GroupCount> GroupBy(const std::vector<std::string>& fields, const Call* filter, const std::string& agg_field, const GroupByOptions& opt) {
+    if (fields.empty()) throw Error(FBK_E_INVALID, "need at least one child call");  // executor.go:3927
+    fbk_groupby_select sel{};
+    if (!opt.sort.empty())
+      for (const fbk_groupby_term& t : ParseGroupBySort(opt.sort)) {
+        bool seen = false;
+        for (uint32_t k = 0; k < sel.n_sort; ++k) seen = seen || sel.sort[k].subject == t.subject;
+        if (!seen) sel.sort[sel.n_sort++] = t;  // (a repeated subject never decides; count and sum: at most two terms stay)
+      }
+    if (opt.having) {
+      const GroupByCondition& h = *opt.having;
+      if (h.subject != "count" && h.subject != "sum") throw Error(FBK_E_INVALID, "Condition() only supports count or sum");
+      if (h.op < FBK_HAVING_EQ || h.op > FBK_HAVING_BTWN_LT_LT) throw Error(FBK_E_INVALID, "Condition(): unknown operator");
+      sel.having_subject = h.subject == "count" ? FBK_GROUPSEL_COUNT : FBK_GROUPSEL_AGG;
+      sel.having_op = h.op, sel.having_lo = h.lo, sel.having_hi = h.hi;
+      if (h.subject == "count" && (h.lo < 0 || (h.op >= FBK_HAVING_BETWEEN && h.hi < 0))) return {};  // Uint64Value fails: nothing matches
+    }
+    const bool plain = sel.n_sort == 0 && !opt.having;
+    uint64_t offset = opt.offset.value_or(0), limit = opt.limit.value_or(UINT64_MAX);
+    if (plain && opt.limit) {  // the merge kept the first L groups; offset and limit again on those
+      if (offset >= limit) offset = 0;
+      else limit -= offset;
+    }
+    Scope sc(*this, {filter});
+    std::vector<GroupCount> out;
+    const size_t n = shards().size();
+    if (n == 0) return out;
+    std::unique_ptr<RowSet> prefix;
+    if (filter) prefix.reset(new RowSet(eval(*filter)));
+    const fbk_batch* fb_ = prefix ? prefix->batch() : nullptr;
+    const uint32_t* fr_ = prefix ? prefix->rows().data() : nullptr;
+    std::vector<const Index::SetField*> fs;
+    uint64_t cells = 1;
+    bool fits = fields.size() <= 3;
+    for (const std::string& name : fields) {
+      fs.push_back(&idx_.sets_.at(name));
+      const uint64_t nr = fs.back()->row_ids.size();
+      if (nr == 0) return out;
+      fits = fits && nr <= kSumBlock;
+      cells *= std::min<uint64_t>(nr, uint64_t(1) << 25);
+      fits = fits && cells <= kCubeCells;
+    }
+    const Index::IntField* af = agg_field.empty() ? nullptr : &idx_.ints_.at(agg_field);
+    if (af) fits = fits && fields.size() <= 2 && af->base == 0;
+    if (!af && fields.size() == 1 && !prefix) fits = false;  // (the one-field count form takes the filter row as its B: without one, fbk_count's totals)
+    sel.offset = offset, sel.limit = limit;
+    // measured (docs/history/DESIGN_groupby_select_measurements.md): under 2^17 cells a sort that keeps a handful of groups is faster on
+    // the host (251 against 362 us at 2^16 cells, limit 10; even at 2^17): the radix select's 16 launches per term cost more than the transfer
+    if (sel.n_sort && cells <= (uint64_t(1) << 17) && limit <= 64 && offset <= 64) sel.flags = FBK_GROUPSEL_HOST;
+    if (const char* what = fbk_group_select::check(&sel, af != nullptr)) throw Error(FBK_E_INVALID, std::string("GroupBy: ") + what);
+
+    std::vector<uint32_t> cell;
+    std::vector<uint64_t> cnt;
+    std::vector<int64_t> agg;
+    if (fits) {
+      std::vector<std::vector<uint32_t>> rows;
+      for (const Index::SetField* f : fs) rows.push_back(field_rows(*f));
+      const std::vector<uint32_t> base = af ? base_rows(*af) : std::vector<uint32_t>();
+      auto call = [&](uint64_t cap, uint64_t* out_n, uint64_t* matched) -> int32_t {
+        cell.assign(cap, 0), cnt.assign(cap, 0);
+        if (af) agg.assign(cap, 0);
+        const uint32_t r0 = uint32_t(fs[0]->row_ids.size()), r1 = fs.size() > 1 ? uint32_t(fs[1]->row_ids.size()) : 1;
+        if (af)
+          return fbk_count_matrix_sum_select(idx_.ctx_, fs[0]->batch, rows[0].data(), r0, fs.size() > 1 ? fs[1]->batch : nullptr,
+                                             fs.size() > 1 ? rows[1].data() : nullptr, r1, fb_, fr_, af->batch, base.data(), af->bit_depth, uint32_t(n), &sel,
+                                             cell.data(), cnt.data(), agg.data(), cap, out_n, matched);
+        if (fs.size() == 3)
+          return fbk_count_cube_select(idx_.ctx_, fs[0]->batch, rows[0].data(), r0, fs[1]->batch, rows[1].data(), r1, fs[2]->batch, rows[2].data(),
+                                       uint32_t(fs[2]->row_ids.size()), fb_, fr_, uint32_t(n), &sel, cell.data(), cnt.data(), cap, out_n, matched);
+        if (fs.size() == 2)
+          return fbk_count_matrix_select(idx_.ctx_, fs[0]->batch, rows[0].data(), r0, fs[1]->batch, rows[1].data(), r1, fb_, fr_, uint32_t(n), &sel, cell.data(),
+                                         cnt.data(), cap, out_n, matched);
+        return fbk_count_matrix_select(idx_.ctx_, fs[0]->batch, rows[0].data(), r0, fb_, fr_, 1, nullptr, nullptr, uint32_t(n), &sel, cell.data(), cnt.data(), cap,
+                                       out_n, matched);
+      };
+      uint64_t got = 0, matched = 0, cap = std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(limit, 1 << 16), cells));
+      int32_t rc = call(cap, &got, &matched);
+      if (rc == FBK_OK && got == 0 && matched > 0 && sel.offset >= matched) {  // applyLimitAndOffsetToGroupByResult ignores such an offset
+        sel.offset = 0;
+        if (plain && opt.limit) sel.limit = *opt.limit;
+        rc = call(cap, &got, &matched);
+      }
+      if (rc == FBK_E_CAPACITY) rc = call(got, &got, &matched);
+      check(rc);
+      cell.resize(got);
+    } else {
+      GroupAgg ga;
+      ga.sum_field = agg_field;
+      std::vector<FieldRow> group;
+      std::vector<GroupCount> all;
+      group_by_rec(fields, 0, prefix.get(), ga, 0, group, all);
+      std::vector<uint64_t> c(all.size());
+      std::vector<int64_t> a(all.size());
+      for (size_t k = 0; k < all.size(); ++k) c[k] = all[k].Count, a[k] = all[k].Agg;
+      uint64_t matched = fbk_group_select::select(c.data(), af ? a.data() : nullptr, c.size(), sel, cell);
+      if (cell.empty() && matched > 0 && sel.offset >= matched) {
+        sel.offset = 0;
+        if (plain && opt.limit) sel.limit = *opt.limit;
+        fbk_group_select::select(c.data(), af ? a.data() : nullptr, c.size(), sel, cell);
+      }
+      for (uint32_t k : cell) out.push_back(std::move(all[k]));
+      return out;
+    }
+    for (size_t k = 0; k < cell.size(); ++k) {
+      GroupCount g;
+      uint64_t rest = cell[k];
+      g.Group.resize(fs.size());
+      for (size_t f = fs.size(); f-- > 0;) {  // odometer order, the last field fastest
+        const uint64_t nr = fs[f]->row_ids.size();
+        g.Group[f] = {fields[f], fs[f]->row_ids[rest % nr]};
+        rest /= nr;
+      }
+      g.Count = cnt[k];
+      g.Agg = af ? agg[k] : 0;  // (Base is 0 on this path)
+      out.push_back(std::move(g));
+    }
     return out;
   }
 
