@@ -1391,7 +1391,8 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_output.inc"
 #include "fbk_plan_api.inc"
 #include "fbk_dense_operands.inc"
-#include "fbk_query_api.inc"
+#include "fbk_query_api.inc"         // folds, Rows / Flip / Shift / compaction, the BSI aggregates
+#include "fbk_count_matrix_api.inc"  // the GroupBy count matrix: MatrixPlan; its rules: fbk_count_matrix_plan.h
 #include "fbk_matrix_sum_api.inc"
 #include "fbk_count_cube_api.inc"
 #include "fbk_group_select_api.inc"

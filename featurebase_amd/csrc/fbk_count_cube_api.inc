@@ -52,17 +52,15 @@ int32_t cube_enqueue(fbk_ctx* ctx, CubePlan& c) {
   const uint32_t n_p = c.n_p, n_a = c.n_a, n_b = c.n_b;
   HIP_TRY(hipMemsetAsync(c.result.p, 0, cells * 8, ctx->stream));
   KernelSpan span(ctx);
-  // P rows per block: 8 accumulators share one B expansion; a field of at most 4 rows would spend half of them on repeats
-  const uint32_t pt = n_p <= 4 ? 4 : 8;
-  const uint64_t tiles = uint64_t((n_p + pt - 1) / pt) * ((n_a + 31) / 32) * ((n_b + 31) / 32);
+  namespace mp = fbk_count_matrix_plan;  // P rows per block, tiles, slots per block
+  const uint32_t pt = mp::cube_pt(n_p);
+  const uint64_t tiles = mp::cube_tiles(n_p, n_a, n_b);
   for (uint32_t s0 = 0; s0 < c.n_shards; s0 += c.chunk) {
     const uint32_t ns = std::min(c.chunk, c.n_shards - s0);
     c.ops.densify(ctx, s0, ns);
     const DenseView P = c.ops.view(c.P, s0), A = c.ops.view(c.A, s0), B = c.ops.view(c.B, s0), F = c.ops.view(c.F, s0);
     HIP_TRY(hipMemsetAsync(c.dshard.p, 0, uint64_t(ns) * cells * 8, ctx->stream));
-    uint32_t spb = 16;  // slots per block: whole shards while the grid still holds ~2048 blocks, fewer slots (more atomics) below
-    while (spb > 1 && uint64_t(ns) * (16 / spb) * tiles < 2048) spb >>= 1;
-    if (ctx->opt.matrix_spb) spb = uint32_t(ctx->opt.matrix_spb);  // tests walk every value
+    const uint32_t spb = mp::slots_per_block(tiles, ns, mp::kCubeFloor, mp::kCubeEnough, uint32_t(ctx->opt.matrix_spb));  // tests walk every value
     // a launch takes as many of the chunk's shards as a grid has block ids for
     const uint64_t per_shard = (16 / spb) * tiles;
     const uint32_t most = uint32_t(std::min<uint64_t>(ns, std::max<uint64_t>(1, uint64_t(INT32_MAX) / per_shard)));

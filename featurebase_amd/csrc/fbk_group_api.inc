@@ -459,9 +459,10 @@ int32_t fbk_group_count_matrix(fbk_group* g, const fbk_matrix_args* per_member, 
       if (e != hipSuccess) rc = fail(FBK_E_HIP, std::string("hipMemsetAsync: ") + hipGetErrorString(e));
       continue;
     }
-    DevBuf dshard;
-    rc = count_matrix_enqueue_locked(c, a.a, a.rows_a, n_a, a.b, a.rows_b, n_b, a.filter, a.rows_f, a.n_shards, false, dshard, g->d_partial[m]);
-    if (rc) group_drain(g);  // (before dshard goes back to the member's pool)
+    MatrixPlan p;
+    rc = matrix_prepare(c, p, a.a, a.rows_a, n_a, a.b, a.rows_b, n_b, a.filter, a.rows_f, a.n_shards, false);
+    if (!rc) rc = matrix_enqueue(c, p, g->d_partial[m], false);
+    if (rc) group_drain(g);  // (before the plan's buffers go back to the member's pool)
   }
   if (!rc) rc = group_reduce(g, width, out_total);
   if (rc) group_drain(g);

@@ -183,9 +183,11 @@ int32_t fbk_count_matrix_select(fbk_ctx* ctx, const fbk_batch* a, const uint32_t
   if (n_shards == 0 || width == 0) return FBK_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
-  DevBuf dshard, dtot;
+  MatrixPlan p;
+  DevBuf dtot;
   HIP_TRY(dtot.alloc(ctx, width * 8));
-  if (int32_t rc = count_matrix_enqueue_locked(ctx, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, n_shards, false, dshard, dtot.as<u64>())) return rc;
+  if (int32_t rc = matrix_prepare(ctx, p, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, n_shards, false)) return rc;
+  if (int32_t rc = matrix_enqueue(ctx, p, dtot.as<u64>(), false)) return rc;
   return group_select_locked(ctx, dtot.as<u64>(), nullptr, width, *sel, out_cells, out_counts, nullptr, cap, out_n, out_matched);
 } FBK_ABI_CATCH(ctx)
 

@@ -69,9 +69,9 @@ int32_t msum_enqueue(fbk_ctx* ctx, MsumPlan& p) {
     if (p.n_chunks)
       hipLaunchKernelGGL(fbk::k_msum_chunks, dim3(ns * 128u), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, p.depth, p.n_chunks, p.chunks.as<uint8_t>());
     HIP_TRY(hipMemsetAsync(p.dshard.p, 0, uint64_t(ns) * 2 * width * 8, ctx->stream));
-    const uint32_t tiles = ((n_a + 31) / 32) * ((n_b + 31) / 32);
-    uint32_t spb = 16;  // slots per block: whole shards while the grid still holds ~2048 blocks, fewer slots (more atomics) below
-    while (spb > 1 && uint64_t(ns) * (16 / spb) * tiles < 2048) spb >>= 1;
+    namespace mp = fbk_count_matrix_plan;  // slots per block: whole shards while the grid still holds ~2048 blocks
+    const uint32_t tiles = mp::tiles32(n_a, n_b);
+    const uint32_t spb = mp::slots_per_block(tiles, ns, mp::kSumFloor, mp::kSumEnough, 0);
     const dim3 grid(uint32_t(uint64_t(ns) * (16 / spb) * tiles));
     const uint8_t* ch = p.chunks.as<uint8_t>();
     u64* out = p.dshard.as<u64>();

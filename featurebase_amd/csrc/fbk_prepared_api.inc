@@ -23,11 +23,9 @@ struct fbk_query {
   uint32_t n_a = 0, n_b = 0, k = 0, depth = 0;
   int32_t op = 0;
   uint64_t n = 0;  // shards / groups
-  bool keep_per_shard = false;
   DevBuf rows;  // every row list of the query, one allocation
   const uint32_t* dr[3] = {nullptr, nullptr, nullptr};
   DevBuf result;   // count matrix: total [n_a * n_b]; fold: counts [n]; BSI: raw per-shard triples / quadruples
-  DevBuf dshard;   // count matrix: per-shard matrices of one pass
   DevBuf dplan;    // BSI range-sum: the RangeSumPlan
   fbk::RangeSumPlan plan{};
   uint64_t result_bytes = 0;
@@ -47,13 +45,11 @@ struct fbk_query {
   std::unique_ptr<Topn> topn;
   bool ran = false;
   void* last_out = nullptr;  // where the last run wrote (result.p or the caller's buffer)
-  // folds and TopN: the descriptors of every (group / shard, slot) side by side (k_resolve_rows), resolved on the first run and
-  // again whenever the batch's descriptors have been rewritten since (nothing above 1 GiB)
-  DevBuf recs;
-  uint64_t recs_version = ~0ull;
-  // count matrix over encoded rows: the prepared program of the kernel (fbk_matrix_fused.hip.h), built on the first run and again
-  // whenever a batch's descriptors have been rewritten since
-  FxProgram fx;
+  // folds and TopN: the resolved records of the rows dr[0] of `a` (fbk_query_api.inc)
+  RowRecords recs;
+  // the GroupBy count matrix (fbk_count_matrix_api.inc): row lists, per-shard matrices, and what its runs keep — the resolved records
+  // of the TopK shape, the prepared program of the kernel over encoded rows; the totals are in `result`
+  std::unique_ptr<MatrixPlan> matrix;
   // GroupBy with aggregate=Sum (fbk_matrix_sum_api.inc): row lists, scratch and the result {sums, counts}
   std::unique_ptr<MsumPlan> msum;
   // a whole call tree (fbk_expr_api.inc): row lists, leaf table and lowered program; out == nullptr: FBK_EXPR_COUNT_ONLY.
@@ -66,27 +62,6 @@ namespace {
 int32_t query_check(fbk_ctx* ctx, const fbk_query* q) {
   if (!ctx || !q) return fail(FBK_E_INVALID, "NULL argument");
   if (q->ctx != ctx) return fail(FBK_E_INVALID, "query was prepared on another context");
-  return FBK_OK;
-}
-
-// The resolved row records of a fold / TopN query for this run (nullptr: not used).  rows = q->dr[0]: [n_units][n_per].
-int32_t query_row_records(fbk_ctx* ctx, fbk_query* q, uint64_t n_units, uint32_t n_per, const Slot** out) {
-  *out = nullptr;
-  const uint64_t n = n_units * fbk::kSlots * n_per;
-  if (n == 0 || n * sizeof(Slot) > (1ull << 30)) return FBK_OK;
-  if (!q->recs.p) {
-    if (q->recs.alloc(ctx, n * sizeof(Slot)) != hipSuccess) {
-      (void)hipGetLastError();
-      return FBK_OK;  // (no memory for the records: the kernels gather the descriptors themselves)
-    }
-    q->recs_version = ~0ull;
-  }
-  if (q->recs_version != q->a->version) {
-    hipLaunchKernelGGL(fbk::k_resolve_rows, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, q->a->d_slots, q->dr[0], n_units, n_per, q->recs.as<Slot>());
-    HIP_TRY(hipGetLastError());
-    q->recs_version = q->a->version;
-  }
-  *out = q->recs.as<Slot>();
   return FBK_OK;
 }
 
@@ -132,9 +107,10 @@ int32_t fbk_query_count_matrix(fbk_ctx* ctx, const fbk_batch* a, const uint32_t*
   q->n_a = n_a;
   q->n_b = n_b;
   q->n = n_shards;
-  q->keep_per_shard = keep_per_shard != 0;
   q->result_bytes = width * 8;
-  int32_t rc = count_matrix_upload_rows(ctx, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, n_shards, q->rows, q->dr);
+  q->matrix.reset(new MatrixPlan());
+  q->matrix->kept = true;
+  int32_t rc = matrix_prepare(ctx, *q->matrix, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, n_shards, keep_per_shard != 0);
   if (!rc) {
     const hipError_t e = q->result.alloc(ctx, q->result_bytes);
     if (e != hipSuccess) rc = fail(FBK_E_NOMEM, std::string("query: ") + hipGetErrorString(e));
@@ -435,14 +411,9 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
   void* out = device_out ? device_out : q->result.p;
   int32_t rc = FBK_OK;
   switch (q->kind) {
-    case kQCountMatrix: {
-      const Slot* recs = nullptr;
-      if (q->n_b == 1 && !q->filter) rc = query_row_records(ctx, q, q->n, q->n_a, &recs);  // (the TopK shape: k_rows_vs_filter)
-      if (!rc)
-        rc = count_matrix_enqueue_locked(ctx, q->a, nullptr, q->n_a, q->b, nullptr, q->n_b, q->filter, nullptr, uint32_t(q->n), q->keep_per_shard, q->dshard,
-                                         static_cast<u64*>(out), q->dr, acc, recs, &q->fx);
+    case kQCountMatrix:
+      rc = matrix_enqueue(ctx, *q->matrix, static_cast<u64*>(out), acc);
       break;
-    }
     case kQCountMatrixSum:
       if (acc || device_out) return fail(FBK_E_INVALID, "query: a GroupBy Sum writes its own two arrays (fbk_query_read), nothing to accumulate");
       rc = msum_enqueue(ctx, *q->msum);
@@ -450,7 +421,7 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
       break;
     case kQFoldICount: {
       const Slot* recs = nullptr;
-      if (q->op != FBK_OP_AND) rc = query_row_records(ctx, q, q->n, q->k, &recs);  // (the scatter kernels)
+      if (q->op != FBK_OP_AND) rc = query_row_records(ctx, q->recs, q->a, q->dr[0], q->n, q->k, &recs);  // (the scatter kernels)
       if (!rc) rc = fold_n_icount_launch(ctx, q->op, q->a, q->dr, q->n, q->k, q->filter, static_cast<u64*>(out), acc, recs);
       break;
     }
@@ -477,7 +448,7 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
       if (acc) return fail(FBK_E_INVALID, "query: a row result cannot be accumulated");
       const Slot* recs = nullptr;
       if (q->op != FBK_OP_AND)
-        if (int32_t rr = query_row_records(ctx, q, q->n, q->k, &recs)) return rr;
+        if (int32_t rr = query_row_records(ctx, q->recs, q->a, q->dr[0], q->n, q->k, &recs)) return rr;
       HIP_TRY(hipMemsetAsync(out, 0, q->n * 8, ctx->stream));
       {
         KernelSpan span(ctx);
@@ -512,7 +483,7 @@ int32_t fbk_query_run(fbk_ctx* ctx, fbk_query* q, void* device_out, uint32_t fla
       if (acc) return fail(FBK_E_INVALID, "query: TopN totals are ordered by the run, not accumulable");
       if (device_out) return fail(FBK_E_INVALID, "query: a TopN writes its own buffers (fbk_query_read)");
       const Slot* recs = nullptr;
-      if (q->filter) rc = query_row_records(ctx, q, q->n, q->n_a, &recs);  // (k_rows_vs_filter; without a filter the stored cardinalities answer)
+      if (q->filter) rc = query_row_records(ctx, q->recs, q->a, q->dr[0], q->n, q->n_a, &recs);  // (k_rows_vs_filter; without a filter the stored cardinalities answer)
       if (rc) break;
       TopnSort& s = q->topn->sort;
       rc = topn_totals_enqueue(ctx, q->a, q->dr[0], TopnSource{q->filter, q->dr[1], recs}, q->topn->buf, /*mask=*/true);
@@ -555,14 +526,10 @@ int32_t fbk_query_read(fbk_ctx* ctx, fbk_query* q, void* out0, void* out1) try {
   if (int32_t rc = set_device(ctx)) return rc;
   D2H back(ctx);
   switch (q->kind) {
-    case kQCountMatrix: {
+    case kQCountMatrix:
       // out0 = total [n_a * n_b] (may be NULL), out1 = per-shard matrices [n_shards][n_a * n_b] (prepared with keep_per_shard)
-      if (out1 && !q->keep_per_shard) return fail(FBK_E_INVALID, "query: prepared without keep_per_shard");
-      if (out0) HIP_TRY(back.add(out0, q->last_out, q->result_bytes));
-      if (out1) HIP_TRY(back.add(out1, q->dshard.p, q->n * q->result_bytes));
-      HIP_TRY(back.finish());
-      return FBK_OK;
-    }
+      if (out1 && !q->matrix->keep_per_shard) return fail(FBK_E_INVALID, "query: prepared without keep_per_shard");
+      return matrix_read(ctx, *q->matrix, static_cast<const u64*>(q->last_out), static_cast<uint64_t*>(out0), static_cast<uint64_t*>(out1));
     case kQCountMatrixSum:  // out0 = int64 sums [n_a * n_b], out1 = uint64 counts [n_a * n_b]
       return msum_read(ctx, *q->msum, static_cast<int64_t*>(out0), static_cast<uint64_t*>(out1));
     case kQFoldICount:

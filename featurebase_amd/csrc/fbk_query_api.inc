@@ -1,7 +1,8 @@
 // fbk_query_api.inc — host side of the query-level entry points (included by fbk.hip).
-// n-way fold, count matrix (GroupBy, and the launch of k_rows_vs_filter for its TopK shape), Rows, Flip, Shift, and the BSI calls:
-// Range, Sum / Min / Max and the range sums (one frame: BsiShardOperands + download_words), Add, Distinct.  The output batch of the
-// materialising ones is a CellOutput (fbk_output.inc).  TopK / TopN: fbk_topn_api.inc.
+// n-way fold (and the resolved row records its prepared form shares with the count matrix and TopN), Rows, Flip, Shift, compaction,
+// and the BSI calls: Range, Sum / Min / Max and the range sums (one frame: BsiShardOperands + download_words), Add, Distinct.  The
+// output batch of the materialising ones is a CellOutput (fbk_output.inc).  The GroupBy count matrix: fbk_count_matrix_api.inc.
+// TopK / TopN: fbk_topn_api.inc.
 
 namespace {
 
@@ -147,6 +148,35 @@ struct FilterArgs {
     if (filter) slots = filter->d_slots, arena = filter->d_arena, rows = d_rows;
   }
 };
+
+// What a prepared fold, count matrix (TopK shape) or TopN keeps of its field's rows: the descriptors of every (group / shard, slot)
+// side by side (k_resolve_rows), resolved on the first run and again whenever the batch's descriptors have been rewritten since
+// (nothing above 1 GiB).
+struct RowRecords {
+  DevBuf buf;
+  uint64_t version = ~0ull;
+};
+
+// The resolved records of rows d_rows [n_units][n_per] of `a` for this run (nullptr: not used).
+int32_t query_row_records(fbk_ctx* ctx, RowRecords& r, const fbk_batch* a, const uint32_t* d_rows, uint64_t n_units, uint32_t n_per, const Slot** out) {
+  *out = nullptr;
+  const uint64_t n = n_units * fbk::kSlots * n_per;
+  if (n == 0 || n * sizeof(Slot) > (1ull << 30)) return FBK_OK;
+  if (!r.buf.p) {
+    if (r.buf.alloc(ctx, n * sizeof(Slot)) != hipSuccess) {
+      (void)hipGetLastError();
+      return FBK_OK;  // (no memory for the records: the kernels gather the descriptors themselves)
+    }
+    r.version = ~0ull;
+  }
+  if (r.version != a->version) {
+    hipLaunchKernelGGL(fbk::k_resolve_rows, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, ctx->stream, a->d_slots, d_rows, n_units, n_per, r.buf.as<Slot>());
+    HIP_TRY(hipGetLastError());
+    r.version = a->version;
+  }
+  *out = r.buf.as<Slot>();
+  return FBK_OK;
+}
 
 int32_t run_bsi_program(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_rows, uint64_t n_shards,
                         uint64_t bit_depth, const BsiProg& prog, uint32_t flags, fbk_batch** out_batch,
@@ -341,362 +371,6 @@ int32_t fbk_union_n_intersection_count(fbk_ctx* ctx, const fbk_batch* batch, con
                                        uint64_t* out_counts) try {
   FBK_ENTER(ctx);
   return fbk_fold_n_intersection_count(ctx, FBK_OP_OR, batch, rows, n_groups, k, filter, rows_f, out_counts);
-} FBK_ABI_CATCH(ctx)
-
-// Encoded rows: the generic pair kernel (k_count_matrix<4>), or the matrix-core kernel that decodes the rows in place
-// (fbk_matrix_fusedq.hip.h)?  Round 4, scripts/small_shapes_ab.py, 64 shards of config 3's rows, interleaved in one process
-// (profiles/r04_small_shapes_ab.json): the fused kernel costs 65-75 us whatever the shape up to a 32 x 32 tile (it decodes
-// every row once), the generic kernel ~38 us + 1.5 us per pair — 2 x 2: 44 against 65 us, 8 x 8: 139 against 70, 4 x 16: 156
-// against 70, 3 x 30: 241 against 73.  From 16 pairs per shard on the rows are decoded once.  (Rounds 1-4 had a third path —
-// rows densified into temporary bitmap rows, then the dense kernel: 681 + 347 us against ~400 us for the first in-kernel
-// decode on 256 shards of config 3's rows, never chosen since round 2 — removed in round 5.)
-static bool matrix_prefers_fused(uint32_t n_a, uint32_t n_b) { return uint64_t(n_a) * n_b >= 16; }
-
-// The dense count-matrix launch: the matrix-core kernel (fbk_matrix_mfma.hip.h).
-// A block covers `spb` of a shard's 16 slots: whole shards (plain stores) when that still gives
-// two blocks per CU, otherwise fewer slots per block (atomic adds into the per-shard matrix);
-// FBK_MATRIX_SPB=1|2|4|8|16 pins it (tests walk every value).
-static void launch_matrix_dense(fbk_ctx* ctx, const uint8_t* arenaA, const uint32_t* rowsA, uint32_t n_a, const uint8_t* arenaB,
-                                const uint32_t* rowsB, uint32_t n_b, const uint8_t* arenaF, const uint32_t* rowsF,
-                                uint32_t n_shards, u64* out_shard) {
-  // a side of more than 32 rows gets two 32-row tiles per block: the operand expansion of the
-  // other side is reused, which is what bounds a matrix of many tiles (scripts/tune_matrix.hip)
-  const uint32_t tm = n_a > 32 ? 2 : 1, tn = n_b > 32 ? 2 : 1;
-  const uint32_t tiles = ((n_a + 32 * tm - 1) / (32 * tm)) * ((n_b + 32 * tn - 1) / (32 * tn));
-  // Slots per block: 2 blocks fit a CU, so 512 run at a time — with one block per shard (spb 16) the 1024 shards a rank of BASELINE
-  // configs[3] owns are two rounds of ~700 us blocks and whatever the slowest CU loses shows in full; ~8192 blocks (16 rounds)
-  // even that out at the price of atomic adds into the per-shard matrix.  scripts/matrix_spb_sweep.py, 1024 shards x 32 x 32 +
-  // filter, interleaved in one process (profiles/r04_matrix_spb_sweep.json): spb 16 1382 us (1356 .. 1443), spb 4 1372 (1368 ..
-  // 1388), spb 2 1364 (1354 .. 1379): from ~4096 blocks (8 rounds) on it no longer matters.
-  uint32_t spb = 16;
-  while (spb > 2 && uint64_t(n_shards) * (16 / spb) * tiles < 4096) spb >>= 1;
-  if (ctx->opt.matrix_spb) spb = uint32_t(ctx->opt.matrix_spb);  // tests walk every value
-  uint32_t blocks = n_shards * (16 / spb) * tiles;
-  // A single-tile matrix (the HBM-bound shape) takes its units by TICKET, long units first (fbk_matrix_mfma.hip.h): the XCDs do not
-  // run at one pace, and a launch by block id gives each an eighth of the work whatever its pace.  matrix_tickets = 0 pins the
-  // launch by block id (the A/B and the cross-check).
-  fbk::MmTickets tk{0, 0, 0, 0};
-  uint32_t* d_ticket = nullptr;
-  if (tiles == 1 && ctx->opt.matrix_tickets && fbk::mm_ticket_plan(n_shards, spb, 2u * uint32_t(std::max(ctx->n_cu, 1)), tk) && ticket_counter(ctx, &d_ticket) == FBK_OK)
-    blocks = tk.grid;
-  constexpr int W = fbk::kMmWaves, D = fbk::kMmDepth, AUX = fbk::kMmAux;
-#define FBK_MM(F, TM, TN, P4)                                                                                                        \
-  hipLaunchKernelGGL((fbk::k_count_matrix_mfma<F, W, D, AUX, TM, TN, P4>), dim3(blocks), dim3(W * 64), 0, ctx->stream, arenaA, rowsA, \
-                     n_a, arenaB, rowsB, n_b, arenaF, rowsF, n_shards, spb, out_shard, d_ticket, tk.tier0_shards, tk.tier1_shards, tk.tier_spb)
-#define FBK_MM_F(TM, TN)                      \
-  do {                                        \
-    if (arenaF && fp4) FBK_MM(true, TM, TN, true);   \
-    else if (arenaF) FBK_MM(true, TM, TN, false);    \
-    else if (fp4) FBK_MM(false, TM, TN, true);       \
-    else FBK_MM(false, TM, TN, false);               \
-  } while (0)
-  // matrix_fp4: 1 / 0 pins the FP4 matrix instruction, -1: matrices of several tiles (matrix-core
-  // bound) use it, a single 32 x 32 tile (HBM-bound) stays on the i8 instruction
-  const bool fp4 = ctx->opt.matrix_fp4 == 1 || (ctx->opt.matrix_fp4 < 0 && tiles > 1);
-  if (tm == 2 && tn == 2) FBK_MM_F(2, 2);
-  else if (tm == 2) FBK_MM_F(2, 1);
-  else if (tn == 2) FBK_MM_F(1, 2);
-  else FBK_MM_F(1, 1);
-#undef FBK_MM_F
-#undef FBK_MM
-}
-
-}  // extern "C"
-
-namespace {
-
-int32_t count_matrix_args_ok(const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b, const uint32_t* rows_b,
-                             uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f, uint32_t n_shards) {
-  if (!a || !b || (n_shards && n_a && !rows_a) || (n_shards && n_b && !rows_b) || (filter && n_shards && !rows_f))
-    return fail(FBK_E_INVALID, "NULL argument");
-  // a matrix is bounded by its nA x nB result; the TopK / TopN shape (one B row) takes fields with
-  // millions of rows
-  if (n_b == 1 ? n_a > (1u << 22) : (n_a > 4096 || n_b > 4096))
-    return fail(FBK_E_INVALID, "count_matrix: at most 4096 rows per side (2^22 rows against a single row)");
-  return FBK_OK;
-}
-
-// Everything of fbk_count_matrix up to the result download: the totals over this context's shards
-// end up in d_total (device, n_a * n_b uint64, zeroed here) and — when keep_per_shard — the
-// per-shard matrices in dshard.  Launch-only: the caller (the one-device entry point, or the
-// multi-device group reduce of fbk_group_api.inc) decides how the totals leave the device.
-// the three row-index lists of a count matrix, validated and made device resident in ONE copy
-int32_t count_matrix_upload_rows(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
-                                 const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f, uint32_t n_shards,
-                                 DevBuf& drows, const uint32_t** dr) {
-  if (int32_t rc = check_rows(rows_a, uint64_t(n_shards) * n_a, a->n_rows, "count_matrix A")) return rc;
-  if (int32_t rc = check_rows(rows_b, uint64_t(n_shards) * n_b, b->n_rows, "count_matrix B")) return rc;
-  return upload_rows_multi(ctx,
-                           {{rows_a, uint64_t(n_shards) * n_a, UINT32_MAX}, {rows_b, uint64_t(n_shards) * n_b, UINT32_MAX},
-                            {rows_f, filter ? uint64_t(n_shards) : 0, filter ? filter->n_rows : UINT32_MAX}},
-                           drows, dr);
-}
-
-// The prepared program of a count matrix over encoded rows (fbk_matrix_fused.hip.h): row tables and resolved array items
-// of every (shard, 32 x 32 tile, container slot) of ONE pass.  It depends on the descriptors of the three batches (their
-// versions; the shadow descriptor tables when the heavy containers are shadowed) and on the row lists; a prepared query keeps
-// it between runs, a one-shot call builds it, uses it and drops it.
-struct FxProgram {
-  DevBuf prog, items, cursor;
-  uint64_t va = ~0ull, vb = ~0ull, vf = ~0ull;
-  const void *sa = nullptr, *sb = nullptr, *sf = nullptr, *ra = nullptr, *rb = nullptr, *rf = nullptr;
-  uint32_t pn = 0, n_a = 0, n_b = 0;
-  uint64_t n_items = 0;
-  bool valid = false;
-};
-
-int32_t fused_program_build(fbk_ctx* ctx, FxProgram& fp, const fbk_batch* a, const Slot* sla, const uint4* wa, const uint32_t* ra, uint32_t n_a, const fbk_batch* b,
-                            const Slot* slb, const uint4* wb, const uint32_t* rb, uint32_t n_b, const fbk_batch* filter, const Slot* slf, const uint4* wf,
-                            const uint32_t* rf, uint32_t pn, bool kept = false) {
-  const uint64_t vf = filter ? filter->version : 0;
-  if (fp.valid && fp.va == a->version && fp.vb == b->version && fp.vf == vf && fp.sa == sla && fp.sb == slb && fp.sf == slf && fp.ra == ra && fp.rb == rb && fp.rf == rf &&
-      fp.pn == pn && fp.n_a == n_a && fp.n_b == n_b)
-    return FBK_OK;
-  fp.valid = false;
-  const uint64_t agroups = (n_a + 31) / 32, btiles = (n_b + 31) / 32;
-  const uint64_t units = uint64_t(pn) * agroups * btiles * fbk::kSlots;
-  // items: k_fused_program emits ceil(values / 128) items per array row OCCURRENCE and stage.  A first guess — every row an item in
-  // every stage plus one per 256 payload bytes of the three arenas, at most 4 M items (64 MB) — is right when every batch row is
-  // listed about once; the kernel counts what it needs whether or not it fits (one atomic per unit), so a pass that lists rows
-  // many times over (duplicates in a row list, one row broadcast to every shard) or a small pass over a multi-GB batch gets a
-  // second launch with exactly that many.
-  const uint64_t guess = units * uint64_t(fbk::kFxNR) * fbk::kFxStages + (a->arena_bytes * btiles + b->arena_bytes * agroups + (filter ? filter->arena_bytes * agroups * btiles : 0)) / 256 + 64;
-  uint64_t cap = std::min<uint64_t>(guess, 4ull << 20);
-  HIP_TRY(fp.prog.ensure(ctx, units * sizeof(fbk::FxProg)));
-  HIP_TRY(fp.cursor.ensure(ctx, 16));
-  const dim3 grid(uint32_t((units + 3) / 4));
-  u64 cur[2] = {0, 0};
-  for (int attempt = 0;; ++attempt) {
-    if (cap > 0xFFFFFFFFull) return fail(FBK_E_INVALID, "count_matrix: more than 2^32 array items in one pass (lower matrix_pass_kb)");
-    HIP_TRY(fp.items.ensure(ctx, std::max<uint64_t>(cap, 1) * sizeof(fbk::FxItem)));
-    HIP_TRY(hipMemsetAsync(fp.cursor.p, 0, 16, ctx->stream));
-    if (filter)
-      hipLaunchKernelGGL(fbk::k_fused_program<true>, grid, dim3(256), 0, ctx->stream, sla, a->d_arena, wa, ra, n_a, slb, b->d_arena, wb, rb, n_b, slf, filter->d_arena, wf, rf, pn,
-                         fp.prog.as<fbk::FxProg>(), fp.items.as<fbk::FxItem>(), fp.cursor.as<u64>(), u64(cap));
-    else
-      hipLaunchKernelGGL(fbk::k_fused_program<false>, grid, dim3(256), 0, ctx->stream, sla, a->d_arena, wa, ra, n_a, slb, b->d_arena, wb, rb, n_b, (const Slot*)nullptr,
-                         (const uint8_t*)nullptr, (const uint4*)nullptr, (const uint32_t*)nullptr, pn, fp.prog.as<fbk::FxProg>(), fp.items.as<fbk::FxItem>(), fp.cursor.as<u64>(),
-                         u64(cap));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(cur, fp.cursor.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (!cur[1]) break;
-    if (attempt || cur[0] <= cap) return fail(FBK_E_INVALID, "count_matrix: the program's item area was too small (a corrupt window index?)");
-    cap = cur[0];  // what the pass needs: counted by the launch that did not fit
-  }
-  fp.n_items = cur[0];
-  // the item area was sized by a guess: a program that
-  // stays — a prepared query's — keeps only what was written (the items' indexes are relative to the area: nothing else moves)
-  if (kept && fp.n_items * sizeof(fbk::FxItem) * 2 < cap * sizeof(fbk::FxItem) && cap * sizeof(fbk::FxItem) > (8u << 20)) {
-    DevBuf tight;
-    if (tight.alloc(ctx, std::max<uint64_t>(fp.n_items, 1) * sizeof(fbk::FxItem)) == hipSuccess) {
-      HIP_TRY(hipMemcpyAsync(tight.p, fp.items.p, fp.n_items * sizeof(fbk::FxItem), hipMemcpyDeviceToDevice, ctx->stream));
-      HIP_TRY(hipStreamSynchronize(ctx->stream));
-      std::swap(tight.p, fp.items.p);
-      std::swap(tight.cap, fp.items.cap);
-      std::swap(tight.c, fp.items.c);
-    } else {
-      (void)hipGetLastError();
-    }
-  }
-  fp.va = a->version, fp.vb = b->version, fp.vf = vf, fp.sa = sla, fp.sb = slb, fp.sf = slf, fp.ra = ra, fp.rb = rb, fp.rf = rf, fp.pn = pn, fp.n_a = n_a, fp.n_b = n_b;
-  fp.valid = true;
-  return FBK_OK;
-}
-
-// THE launch of k_rows_vs_filter (the count matrix's TopK shape below, TopN over a filter row in fbk_topn_api.inc): pn shards,
-// shard s counts rows ra[s][0 .. n_a) of `a` against row rf[s] of `f` into d_out [pn][n_a] (zeroed by the caller); recs: the
-// resolved records of a's rows or nullptr.  The rows per block are fbk_expr::rows_per_block with no tree to re-evaluate (L = 0).
-void launch_rows_vs_filter(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* ra, uint32_t n_a, const fbk_batch* f, const uint32_t* rf, uint32_t pn, u64* d_out,
-                           const Slot* recs) {
-  const uint32_t rpb = fbk_expr::rows_per_block(n_a, pn, 0);
-  const uint32_t chunks = (n_a + rpb - 1) / rpb;
-  hipLaunchKernelGGL(fbk::k_rows_vs_filter, dim3(pn * 16 * chunks), dim3(256), 0, ctx->stream, a->d_slots, a->d_arena, ra, n_a, f->d_slots, f->d_arena, rf, pn, rpb,
-                     d_out, recs);
-}
-
-// d_rows != nullptr: the row lists are already on the device (a prepared query, fbk_query_*): {A, B, filter};
-// then accumulate = true leaves what d_total holds in place and adds to it
-int32_t count_matrix_enqueue_locked(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
-                                    const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
-                                    uint32_t n_shards, bool keep_per_shard, DevBuf& dshard, u64* d_total,
-                                    const uint32_t* const* d_rows = nullptr, bool accumulate = false, const Slot* recs_a = nullptr, FxProgram* program = nullptr) {
-  const uint64_t width = uint64_t(n_a) * n_b;
-  const uint64_t* out_per_shard = keep_per_shard ? reinterpret_cast<const uint64_t*>(1) : nullptr;
-  DevBuf drows;
-  struct {
-    u64* p;
-  } dtot{d_total};
-  const uint32_t* dr[3] = {nullptr, nullptr, nullptr};  // rows of A, B and the filter: one upload
-  if (d_rows) {
-    dr[0] = d_rows[0];
-    dr[1] = d_rows[1];
-    dr[2] = d_rows[2];
-  } else if (int32_t rc = count_matrix_upload_rows(ctx, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, n_shards, drows, dr)) {
-    return rc;
-  }
-  const uint32_t *dra = dr[0], *drb = dr[1], *drf = filter ? dr[2] : nullptr;
-  // The per-shard matrices live in dshard (the reference's per-shard map results).  When the caller
-  // does not ask for them they are only an intermediate of the reduce over shards, so the shards
-  // are processed in passes of at most ~1 GiB of per-shard matrices each (a 1000 x 1000 GroupBy over
-  // 1024 shards would otherwise need 8 GB for them).
-  const uint64_t pass_bytes = uint64_t(ctx->opt.matrix_pass_kb) << 10;  // tests force several passes
-  const uint64_t pass_shards = out_per_shard ? n_shards : std::max<uint64_t>(1, std::min<uint64_t>(n_shards, pass_bytes / (width * 8)));
-  // (a prepared query keeps its own between runs: sized for THIS run's pass — option matrix_pass_kb may have been
-  // raised since the run that allocated it)
-  HIP_TRY(dshard.ensure(ctx, pass_shards * width * 8));
-  if (!accumulate) HIP_TRY(hipMemsetAsync(dtot.p, 0, width * 8, ctx->stream));
-  const int fused_mode = int(ctx->opt.matrix_fused);  // 1 / 0 pins the in-kernel decode / the generic pair kernel, -1: by the matrix size (matrix_prefers_fused)
-  auto run_pass = [&](uint32_t p0, uint32_t pn) -> int32_t {  // shards [p0, p0 + pn) -> dshard[0 .. pn)
-    const uint32_t* ra = dra + uint64_t(p0) * n_a;
-    const uint32_t* rb = drb + uint64_t(p0) * n_b;
-    const uint32_t* rf = filter ? drf + p0 : nullptr;
-    const FilterArgs f(filter, rf);
-    u64* d_out = dshard.as<u64>();
-    HIP_TRY(hipMemsetAsync(d_out, 0, uint64_t(pn) * width * 8, ctx->stream));
-    {
-    KernelSpan span(ctx);
-    FxProgram pass_program;  // (a pass of a one-shot call, or one of several passes: built, used, dropped)
-    if (n_b == 1 && !filter) {
-      // many rows x one row (doTopK / fragment.top): the single B row is the filter of k_rows_vs_filter
-      launch_rows_vs_filter(ctx, a, ra, n_a, b, rb, pn, d_out, recs_a ? recs_a + uint64_t(p0) * fbk::kSlots * n_a : (const Slot*)nullptr);
-    } else if (a->dense && b->dense && (!filter || filter->dense) && n_b > 1) {
-      // every container a bitmap at a fixed address: the matrix-core kernel (fbk_matrix_mfma.hip.h)
-      launch_matrix_dense(ctx, a->d_arena, ra, n_a, b->d_arena, rb, n_b,
-                          f.arena, rf, pn, d_out);
-    } else if (n_b > 1 && fused_mode != 0 && (fused_mode == 1 || matrix_prefers_fused(n_a, n_b))) {
-      // array / run containers among the rows: decoded inside the matrix-core kernel, a stage of 8192
-      // bit positions at a time (fbk_matrix_fused.hip.h) — the encoded payload is the only HBM traffic
-      // and no temporary rows are allocated.  ~400 us against 681 + 347 us for densify + dense kernel on
-      // 256 shards of config 3's rows; the kernel is bound by instruction issue (DESIGN.md section 9).
-      // matrix_fused=0 selects the two-kernel path below.
-      // One block per (shard, slot group, 32 x 32 tile); its 160 KB of LDS give one block per CU at a time.
-      const uint32_t tiles = ((n_a + 31) / 32) * ((n_b + 31) / 32);
-      // (one block per CU at a time; a block builds its work lists once per slot and pays a set-up and a final reduction, so
-      // fewer, longer blocks win as long as every CU has one: 256 shards, spb 16 / 8 / 4 / 2 = 256 / 512 / 1024 / 2048 blocks:
-      // 329 / 333 / 339 / 355 us, profiles/r04_fused_spb_sweep.json)
-      uint32_t spb = 16;
-      while (spb > 2 && uint64_t(pn) * (16 / spb) * tiles < uint64_t(std::max(ctx->n_cu, 1))) spb >>= 1;
-      if (ctx->opt.matrix_spb) spb = uint32_t(ctx->opt.matrix_spb);
-      // (units by ticket, as launch_matrix_dense takes them, were tried here in round 6 — profiles/r06_tickets_ab_fused.json: config 3's 256
-      // shards 261 -> 284 us at 4 slots per unit, config 4's log-uniform rows 1013 -> 1032 us: this kernel is bound by the CU's instruction
-      // issue, not by HBM, so the XCDs' different memory paces do not show, and a ticket costs an atomic round trip that nothing hides with
-      // one block per CU)
-      const uint32_t blocks = pn * (16 / spb) * tiles;
-#ifdef FBK_EXPERIMENTS
-      const uint32_t abl = uint32_t(ctx->opt.matrix_fused_ablate);
-#else
-      constexpr uint32_t abl = 0;
-#endif
-      {
-        // the batches' window indexes (16 bytes per container, built on first use) are what the kernel's work lists come from
-        const uint4 *wa = nullptr, *wb = nullptr, *wf = nullptr;
-        if (int32_t rc = window_index(ctx, a, &wa)) return rc;
-        if (int32_t rc = window_index(ctx, b, &wb)) return rc;
-        if (filter)
-          if (int32_t rc = window_index(ctx, filter, &wf)) return rc;
-        // heavy containers (runs, long arrays) as dense shadows, built per batch on first use (option matrix_shadow)
-        const Slot *sla = a->d_slots, *slb = b->d_slots, *slf = f.slots;
-        bool sha = false, shb = false, shf = false;
-        if (int32_t rc = heavy_shadow(ctx, a, &sla, &sha)) return rc;
-        if (int32_t rc = heavy_shadow(ctx, b, &slb, &shb)) return rc;
-        if (filter)
-          if (int32_t rc = heavy_shadow(ctx, filter, &slf, &shf)) return rc;
-#ifdef FBK_EXPERIMENTS
-        if (filter && (abl & 32u)) {
-          // timing experiment: the instrumented build; the cycle stamps of the grid's middle block go to stderr
-          DevBuf dprof;
-          constexpr size_t kProfWords = size_t(fbk::kFxWaves) * 24 * 8;
-          HIP_TRY(dprof.alloc(ctx, kProfWords * 8));
-          HIP_TRY(hipMemsetAsync(dprof.p, 0, kProfWords * 8, ctx->stream));
-          FxProgram fpp;
-          if (int32_t rc = fused_program_build(ctx, fpp, a, sla, wa, ra, n_a, b, slb, wb, rb, n_b, filter, slf, wf, rf, pn)) return rc;
-          hipLaunchKernelGGL((fbk::k_count_matrix_fusedq<true, true>), dim3(blocks), dim3(fbk::kFxWaves * 64), 0, ctx->stream, fpp.prog.as<fbk::FxProg>(),
-                             fpp.items.as<fbk::FxItem>(), n_a, n_b, pn, spb, d_out, dprof.as<u64>(), abl & 31u);
-          HIP_TRY(hipStreamSynchronize(ctx->stream));
-          std::vector<u64> h(kProfWords);
-          HIP_TRY(hipMemcpyAsync(h.data(), dprof.p, kProfWords * 8, hipMemcpyDeviceToHost, ctx->stream));
-          HIP_TRY(hipStreamSynchronize(ctx->stream));
-          u64 t0 = ~0ull;
-          for (u64 v : h)
-            if (v) t0 = std::min(t0, v);
-          std::fprintf(stderr, "[fused prof] block %u of %u; per stage and wave, cycles since the block's first stamp: start/loads/bitmaps/arrays/runs/barrier\n", blocks / 2, blocks);
-          for (uint32_t st = 0; st < 24; ++st) {
-            if (!h[(size_t(fbk::kFxConsumers) * 24 + st) * 8 + 5] && !h[(0 * 24 + st) * 8 + 5]) continue;
-            for (uint32_t w = 0; w < uint32_t(fbk::kFxWaves); ++w) {
-              const u64* q = &h[(size_t(w) * 24 + st) * 8];
-              std::fprintf(stderr, "st %2u %c%-2u", st, w < uint32_t(fbk::kFxConsumers) ? 'c' : 'p', w);
-              for (int k = 0; k < 6; ++k) std::fprintf(stderr, " %7lld", q[k] ? (long long)(q[k] - t0) : -1ll);
-              std::fprintf(stderr, "\n");
-            }
-          }
-        } else
-#endif
-        {
-          // the prepared program (row tables + resolved array items), then the kernel that runs it
-          FxProgram& fp = (program && p0 == 0 && pn == n_shards) ? *program : pass_program;
-          if (int32_t rc = fused_program_build(ctx, fp, a, sla, wa, ra, n_a, b, slb, wb, rb, n_b, filter, slf, wf, rf, pn, &fp != &pass_program)) return rc;
-          span.restart();
-          const fbk::FxProg* pp = fp.prog.as<fbk::FxProg>();
-          const fbk::FxItem* pi = fp.items.as<fbk::FxItem>();
-          if (filter)
-            hipLaunchKernelGGL((fbk::k_count_matrix_fusedq<true, false>), dim3(blocks), dim3(fbk::kFxWaves * 64), 0, ctx->stream, pp, pi, n_a, n_b, pn, spb, d_out, (u64*)nullptr,
-                               abl & 31u);
-          else
-            hipLaunchKernelGGL((fbk::k_count_matrix_fusedq<false, false>), dim3(blocks), dim3(fbk::kFxWaves * 64), 0, ctx->stream, pp, pi, n_a, n_b, pn, spb, d_out, (u64*)nullptr,
-                               abl & 31u);
-        }
-      }
-    } else {
-      constexpr int TA = 4;
-      const uint32_t agroups = (n_a + 8 * TA - 1) / (8 * TA);
-      // enough blocks to fill 256 CUs: whole rows per block (plain stores) when there are many
-      // shards, otherwise split the 16 slots over several blocks (atomic adds into dshard)
-      uint32_t spb = 16;
-      while (spb > 1 && uint64_t(pn) * (16 / spb) * agroups < 1024) spb >>= 1;
-      const uint32_t blocks = pn * (16 / spb) * agroups;
-      for (uint32_t j0 = 0; j0 < n_b; j0 += 256) {
-        const uint32_t nbc = std::min<uint32_t>(256, n_b - j0);
-        hipLaunchKernelGGL(fbk::k_count_matrix<TA>, dim3(blocks), dim3(512), 0, ctx->stream, a->d_slots, a->d_arena,
-                           ra, n_a, b->d_slots, b->d_arena, rb, n_b, j0, nbc, f.slots, f.arena, rf, pn, spb, d_out);
-      }
-    }
-    }
-    hipLaunchKernelGGL(fbk::k_reduce_shards, dim3(uint32_t((width + 255) / 256), std::min<uint32_t>(pn, 64)), dim3(256), 0,
-                       ctx->stream, d_out, pn, width, dtot.p);
-    HIP_TRY(hipGetLastError());
-    return FBK_OK;
-  };
-  for (uint64_t p0 = 0; p0 < n_shards; p0 += pass_shards)
-    if (int32_t rc = run_pass(uint32_t(p0), uint32_t(std::min<uint64_t>(pass_shards, n_shards - p0)))) return rc;
-  return FBK_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t fbk_count_matrix(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
-                         const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
-                         uint32_t n_shards, uint64_t* out_total, uint64_t* out_per_shard) try {
-  FBK_ENTER(ctx);
-  if (!ctx) return fail(FBK_E_INVALID, "NULL argument");
-  if (int32_t rc = count_matrix_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, n_shards)) return rc;
-  const uint64_t width = uint64_t(n_a) * n_b;
-  if (out_total) std::memset(out_total, 0, width * 8);
-  if (n_shards == 0 || width == 0) return FBK_OK;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int32_t rc = set_device(ctx)) return rc;
-  DevBuf dshard, dtot;
-  HIP_TRY(dtot.alloc(ctx, width * 8));
-  if (int32_t rc = count_matrix_enqueue_locked(ctx, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, n_shards, out_per_shard != nullptr, dshard,
-                                               dtot.as<u64>()))
-    return rc;
-  D2H back(ctx);
-  if (out_total) HIP_TRY(back.add(out_total, dtot.p, width * 8));
-  if (out_per_shard) HIP_TRY(back.add(out_per_shard, dshard.p, uint64_t(n_shards) * width * 8));
-  HIP_TRY(back.finish());
-  return FBK_OK;
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_batch_compact(fbk_ctx* ctx, fbk_batch* batch, uint64_t* out_arena_bytes) try {

@@ -425,3 +425,74 @@ def test_freeing_the_hot_plan(gpu_ctx, small_rows):
         plan.free()
     finally:
         A.free()
+
+
+def _mixed_field(rng, n_rows, p_slot):
+    """n_rows rows of array / run / bitmap containers (encodings by datagen.fbk_container_of_vals, each slot present with
+    probability p_slot) and their words [n_rows, 16, 1024]"""
+    rows, words = [], np.zeros((n_rows, 16, 1024), dtype=np.uint64)
+    for r in range(n_rows):
+        row = {}
+        for s in np.nonzero(rng.random(16) < p_slot)[0]:
+            kind = int(rng.integers(8))
+            if kind == 0:
+                vals = D.vals_density(rng, 0.3)  # a bitmap
+            elif kind <= 3:
+                vals = D.vals_runs(rng, int(rng.choice([16, 128, 1024])), 0.4)
+            else:
+                vals = np.unique(rng.integers(0, 65536, int(rng.integers(1, 3000)))).astype(np.int64)  # an array
+            row[r * 16 + int(s)] = D.fbk_container_of_vals(vals)
+            words[r, s] = D.words_of(vals)
+        rows.append(row)
+    return rows, words
+
+
+def test_a_kept_count_matrix_plan_across_its_modes(gpu_ctx):
+    """One prepared count matrix run under a changing option matrix_pass_kb — one pass over the 3 shards (a program that is kept,
+    records resolved once), one shard per pass (72 cells are 576 B, 200 cells 1600 B: three passes, each with a program of its own),
+    one pass again — then accumulated into its own result; beside it the one-shot calls.  Encoded rows through the in-kernel
+    decode, dense batches, and the TopK shape (200 rows against one, no filter); counts against numpy popcounts of the same rows."""
+    from featurebase_amd.roaring import GroupSelect
+
+    ns, per = 3, 200
+    rng = D.rng_for(8300)
+    head, hw = _mixed_field(rng, ns * 18, 0.85)   # per shard 9 rows of A, 8 of B, the filter row
+    tail, tw = _mixed_field(rng, ns * per, 0.1)   # per shard 200 sparse rows of a third field
+    kinds = {c.typ for r in head + tail for c in r.values()}
+    assert kinds == {L.TYPE_ARRAY, L.TYPE_RUN, L.TYPE_BITMAP}
+    M = gpu_ctx.upload(head + [{k + ns * 18 * 16: c for k, c in r.items()} for r in tail])
+    dw = D.dense_rows(ns * 18, 0.5, 8301)
+    Dn = gpu_ctx.upload_dense(dw)
+    g = np.arange(ns * 18).reshape(ns, 18)
+    ra, rb, rf = g[:, :9], g[:, 9:17], g[:, 17]
+    rt = ns * 18 + np.arange(ns * per).reshape(ns, per)
+
+    def matrix(w):  # [n_a, n_b] over the shards
+        return np.array([[sum(int(np.bitwise_count(w[ra[s, i]] & w[rb[s, j]] & w[rf[s]]).sum()) for s in range(ns)) for j in range(8)] for i in range(9)], dtype=np.uint64)
+
+    topk = np.array([[sum(int(np.bitwise_count(tw[s * per + i] & hw[rf[s]]).sum()) for s in range(ns))] for i in range(per)], dtype=np.uint64)
+    shapes = [("encoded", M, ra, M, rb, M, rf, matrix(hw), 1), ("dense", Dn, ra, Dn, rb, Dn, rf, matrix(dw), -1),
+              ("topk", M, rt, M, rf.reshape(ns, 1), None, None, topk, -1)]
+    assert all(exp.any() for *_, exp, _ in shapes)
+    kept = {o: gpu_ctx.get_option(o) for o in ("matrix_pass_kb", "matrix_fused")}
+    try:
+        for name, A, a, B, b, F, f, exp, fused in shapes:
+            gpu_ctx.set_option("matrix_fused", fused)
+            q = gpu_ctx.prepare_count_matrix(A, a, B, b, F, f)
+            for kb in (1 << 20, 1, 1 << 20):
+                gpu_ctx.set_option("matrix_pass_kb", kb)
+                q.run()
+                assert (q.read() == exp).all(), (name, kb)
+                assert (gpu_ctx.count_matrix(A, a, B, b, F, f) == exp).all(), (name, kb, "one-shot")
+                cells, counts, matched = gpu_ctx.count_matrix_select(A, a, B, b, GroupSelect(), F, f)
+                got = np.zeros(exp.size, dtype=np.uint64)
+                got[cells] = counts
+                assert matched == cells.size == int((exp != 0).sum()) and (got.reshape(exp.shape) == exp).all(), (name, kb, "select")
+            q.run(accumulate=True)  # into the query's own result
+            assert (q.read() == 2 * exp).all(), (name, "accumulate")
+            q.free()
+    finally:
+        for o, v in kept.items():
+            gpu_ctx.set_option(o, v)
+        M.free()
+        Dn.free()
