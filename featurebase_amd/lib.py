@@ -111,6 +111,21 @@ class ExprLeaf(C.Structure):
     ]
 
 
+class I128(C.Structure):
+    """Mirror of fbk_i128 (include/fbk.h): two's complement, hi * 2^64 + lo."""
+
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_int64)]
+
+    def __int__(self) -> int:
+        return self.hi * (1 << 64) + self.lo
+
+
+class Moments(C.Structure):
+    """Mirror of fbk_moments (include/fbk.h): n and the five sums of fbk_bsi_moments, 96 bytes."""
+
+    _fields_ = [("n", C.c_uint64), ("reserved", C.c_uint64), ("sum_x", I128), ("sum_y", I128), ("sum_xx", I128), ("sum_yy", I128), ("sum_xy", I128)]
+
+
 EXPR_ROW, EXPR_BSI, EXPR_BETWEEN = 0, 1, 2
 EXPR_PUSH, EXPR_AND, EXPR_OR, EXPR_XOR, EXPR_ANDNOT = 0, 1, 2, 3, 4
 AGG_SUM, AGG_MIN, AGG_MAX = 0, 1, 2
@@ -172,6 +187,7 @@ SIGNATURES = {
     "fbk_fold_n_intersection_count": (C.c_int32, [_vp, C.c_int32, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp]),
     "fbk_count_matrix": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "fbk_bsi_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "fbk_bsi_moments": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.POINTER(Moments)]),
     "fbk_count_cube": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
     "fbk_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "fbk_query_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),

@@ -10,8 +10,9 @@ This is test/bench plumbing over ctypes; all arithmetic happens in libfbk.so on 
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
-from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -446,6 +447,52 @@ class GroupSelect:
             s.having_lo, s.having_hi = wrap(self.having[2]), wrap(self.having[3])
         s.offset, s.limit = self.offset, (1 << 64) - 1 if self.limit is None else self.limit
         return s
+
+
+class Moments(NamedTuple):
+    """Result of Context.bsi_moments: n and the five sums over the selected columns, Python ints (the sums signed, modulo 2^128)."""
+
+    n: int
+    sum_x: int
+    sum_y: int
+    sum_xx: int
+    sum_yy: int
+    sum_xy: int
+
+
+def moments_shift(m: Moments, base_x: int, base_y: int = 0) -> Moments:
+    """The moments of x + base_x and y + base_y from the raw ones (the four identities of include/fbk.h), in Python ints."""
+    return Moments(
+        m.n,
+        m.sum_x + m.n * base_x,
+        m.sum_y + m.n * base_y,
+        m.sum_xx + 2 * base_x * m.sum_x + m.n * base_x * base_x,
+        m.sum_yy + 2 * base_y * m.sum_y + m.n * base_y * base_y,
+        m.sum_xy + base_y * m.sum_x + base_x * m.sum_y + m.n * base_x * base_y,
+    )
+
+
+def moments_var(m: Moments) -> Optional[int]:
+    """SQL VAR(x) as the reference returns it: the population variance as a decimal of scale 6, truncated toward zero
+    (aggregateVar.Eval, pql.FromFloat64WithScale).  n·Σx² − (Σx)² is exact; one division by n² in double.  None when n == 0:
+    the reference then converts NaN to int64, which Go leaves unspecified."""
+    if m.n == 0:
+        return None
+    return int(float(m.n * m.sum_xx - m.sum_x * m.sum_x) / float(m.n * m.n) * 1e6)
+
+
+def moments_corr(m: Moments) -> Optional[int]:
+    """SQL CORR(x, y) as the reference returns it: the expression of aggregateCorr.Eval in double, in its order of operations,
+    from the moments converted to double; a decimal of scale 6, truncated toward zero.  None when n == 0 or when
+    n·Σx² − (Σx)² or its y counterpart is zero (a constant column): the reference then converts NaN or Inf to int64, which Go
+    leaves unspecified."""
+    if m.n == 0:
+        return None
+    n, sx, sy, sxy, sxx, syy = float(m.n), float(m.sum_x), float(m.sum_y), float(m.sum_xy), float(m.sum_xx), float(m.sum_yy)
+    under = (n * sxx - sx * sx) * (n * syy - sy * sy)
+    if not under > 0 or math.isinf(under):
+        return None
+    return int((n * sxy - sx * sy) / math.sqrt(under) * 1e6)
 
 
 class Context:
@@ -1082,6 +1129,23 @@ class Context:
             )
         )
         return sums, counts
+
+    def bsi_moments(self, x: Batch, base_rows_x, depth_x: int, y: Optional[Batch] = None, base_rows_y=None, depth_y: int = 0,
+                    filt: Optional[Batch] = None, rows_f=None) -> Moments:
+        """n, Σx, Σy, Σx², Σy², Σxy over exists_x ∩ exists_y ∩ filter of all the shards given (fbk_bsi_moments): what SQL VAR
+        and CORR are functions of (moments_var, moments_corr).  y is None: the one-field form.  Base is not applied (moments_shift)."""
+        bx = np.ascontiguousarray(base_rows_x, dtype=np.uint32)
+        by = np.ascontiguousarray(base_rows_y, dtype=np.uint32) if y is not None else None
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        assert (by is None or by.size == bx.size) and (rf is None or rf.size == bx.size)
+        out = L.Moments()
+        L.check(
+            self.lib.fbk_bsi_moments(
+                self.h, x.h, bx.ctypes.data, depth_x, y.h if y is not None else None, by.ctypes.data if by is not None else None, depth_y,
+                filt.h if filt is not None else None, rf.ctypes.data if rf is not None else None, bx.size, C.byref(out),
+            )
+        )
+        return Moments(int(out.n), int(out.sum_x), int(out.sum_y), int(out.sum_xx), int(out.sum_yy), int(out.sum_xy))
 
     def _bsi_minmax(self, fn, batch: Batch, base_rows, bit_depth: int, filt: Optional[Batch], rows_f):
         base = np.ascontiguousarray(base_rows, dtype=np.uint32)

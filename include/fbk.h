@@ -842,6 +842,42 @@ int32_t fbk_bsi_sum(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* base_r
                     uint32_t bit_depth, const fbk_batch* filter, const uint32_t* rows_f, int64_t* out_sums,
                     uint64_t* out_counts);
 
+/* ---- SQL VAR(x) and CORR(x, y): the raw moments of two int fields in one pass -------------------
+ * Over all the shards given, E_s = exists_x ∩ exists_y ∩ F.rows_f[s] (filter == NULL: no filter; the reference skips a row when
+ * either value is nil, sql3/planner/expressionagg.go:978-981):
+ *   n = Σ_s |E_s|,  sum_x = Σ x,  sum_y = Σ y,  sum_xx = Σ x²,  sum_yy = Σ y²,  sum_xy = Σ x·y   over the columns of every E_s,
+ * what aggregateVar (:1110-1195) and aggregateCorr (:949-1047) fold row by row into float accumulators.  Here every sum is an
+ * integer modulo 2^128 (two's complement, as fbk_bsi_sum wraps modulo 2^64): exact whenever the true value fits an int128, which
+ * always holds when depth_x + depth_y + ceil(log2 n) <= 127, and independent of the grid, the chunking and the order.
+ *  - The field layout is fbk_bsi_sum's (base_rows[s] + 0 exists, + 1 sign, + 2 + k plane k), the value of a column
+ *    fbk_extract_bsi's: sign ? -magnitude : magnitude; a set sign over magnitude 0 is 0; sign and plane bits outside exists are
+ *    ignored.  Bit depths 0..64 each.  At most 2^28 shards per call.
+ *  - y == NULL is the one-field form (VAR): depth_y must be 0, E_s = exists_x ∩ F, and sum_y, sum_yy, sum_xy are written as 0.
+ *    x and y may be the same batch and the same field: then sum_xy == sum_xx == sum_yy.
+ *  - Base is NOT applied: VAR and CORR do not depend on it.  A caller that wants the moments of x + bx and y + by shifts them:
+ *      Σ(x+bx) = Σx + n·bx                         Σ(x+bx)² = Σx² + 2·bx·Σx + n·bx²
+ *      Σ(y+by) = Σy + n·by  (Σ(y+by)² alike)       Σ(x+bx)(y+by) = Σxy + by·Σx + bx·Σy + n·bx·by
+ *    A decimal field of scale s stores value · 10^s: VAR scales by 10^(-2s), CORR not at all.
+ *  - NULL ctx, x, base_rows_x or out, a depth above 64, more than 2^28 shards and row indexes beyond a batch give FBK_E_INVALID
+ *    before any launch; every error leaves the context usable.
+ *    n_shards == 0 writes an all-zero struct and returns FBK_OK.  One synchronisation per call.
+ *  - One matrix-core pass over dense rows, every plane read once; rows of batches that are not dense are densified first, a
+ *    chunk of shards at a time: most = max(1, min(n_shards, 2^30 / (2^17 * R))) with R = the rows densified per shard:
+ *    depth_x + 2 if x is not dense, depth_y + 2 if y is not, 1 if the filter is not; chunk = ceil(n_shards / ceil(n_shards /
+ *    most)), the shards dealt evenly over the fewest chunks (R == 0: one chunk). */
+typedef struct fbk_i128 {
+  uint64_t lo;
+  int64_t hi; /* two's complement: hi * 2^64 + lo */
+} fbk_i128;
+typedef struct fbk_moments {
+  uint64_t n;
+  uint64_t reserved;
+  fbk_i128 sum_x, sum_y, sum_xx, sum_yy, sum_xy;
+} fbk_moments; /* 96 bytes */
+int32_t fbk_bsi_moments(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* base_rows_x, uint32_t depth_x, const fbk_batch* y,
+                        const uint32_t* base_rows_y, uint32_t depth_y, const fbk_batch* filter, const uint32_t* rows_f,
+                        uint32_t n_shards, fbk_moments* out);
+
 /* Per shard: (out_vals[s], out_counts[s]) = fragment.min / fragment.max (fragment.go:754-853):
  * the smallest / largest stored value among the columns of exists ∩ filter and the number of
  * columns holding it; (0, 0) when there is no such column.  Sign-magnitude planes, MSB -> LSB

@@ -20,6 +20,7 @@
 // only exists to make the operators testable with the reference's own test vectors.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <memory>
 #include <optional>
@@ -496,6 +497,77 @@ class Executor {
   }
   ValCount Min(const std::string& field, const Call* filter = nullptr) { return minmax(field, filter, true); }
   ValCount Max(const std::string& field, const Call* filter = nullptr) { return minmax(field, filter, false); }
+
+  // ---- SQL VAR / CORR ------------------------------------------------------------------------
+  // aggregateVar / aggregateCorr (sql3/planner/expressionagg.go:1110-1195, 949-1047) fold every selected record into float64
+  // accumulators on the planner.  Here ONE fbk_bsi_moments call gives n and the five integer sums over the columns where
+  // both fields have a value (a row with a nil value is skipped, :978-981) and the filter holds; Base is applied with the
+  // four identities of fbk.h in __int128 (exact while the true sums fit an int128).
+  struct MomentSums {
+    uint64_t n = 0;
+    __int128 sum_x = 0, sum_y = 0, sum_xx = 0, sum_yy = 0, sum_xy = 0;
+  };
+  MomentSums Moments(const std::string& field_x, const std::string* field_y = nullptr, const Call* filter = nullptr) {
+    Scope sc(*this, {filter});
+    const Index::IntField& fx = idx_.ints_.at(field_x);
+    const Index::IntField* fy = field_y ? &idx_.ints_.at(*field_y) : nullptr;
+    const size_t n = shards().size();
+    MomentSums out;
+    if (n == 0) return out;
+    const std::vector<uint32_t> bx = base_rows(fx), by = fy ? base_rows(*fy) : std::vector<uint32_t>();
+    fbk_moments m;
+    if (filter) {  // the filter goes through eval(), as Sum's non-fused path
+      RowSet fr = eval(*filter);
+      check(fbk_bsi_moments(idx_.ctx_, fx.batch, bx.data(), fx.bit_depth, fy ? fy->batch : nullptr, fy ? by.data() : nullptr, fy ? fy->bit_depth : 0, fr.batch(),
+                            fr.rows().data(), uint32_t(n), &m));
+    } else {
+      check(fbk_bsi_moments(idx_.ctx_, fx.batch, bx.data(), fx.bit_depth, fy ? fy->batch : nullptr, fy ? by.data() : nullptr, fy ? fy->bit_depth : 0, nullptr,
+                            nullptr, uint32_t(n), &m));
+    }
+    auto wide = [](const fbk_i128& v) { return __int128((unsigned __int128)(uint64_t)v.hi << 64 | v.lo); };
+    const __int128 cnt = __int128(m.n), sx = wide(m.sum_x), sy = wide(m.sum_y), b = fx.base, c = fy ? fy->base : 0;
+    out.n = m.n;
+    out.sum_x = sx + cnt * b;
+    out.sum_xx = wide(m.sum_xx) + 2 * b * sx + cnt * b * b;
+    if (fy) {
+      out.sum_y = sy + cnt * c;
+      out.sum_yy = wide(m.sum_yy) + 2 * c * sy + cnt * c * c;
+      out.sum_xy = wide(m.sum_xy) + c * sx + b * sy + cnt * b * c;
+    }
+    return out;
+  }
+  // VAR(field): the population variance as a decimal of scale 6.  n·Σx² − (Σx)² is exact in __int128, ONE division by n² in
+  // double, then int64(f * 1e6): truncation toward zero (pql.FromFloat64WithScale, pql/decimal.go:370-373).  The reference sums
+  // (v − mean)² in double over the records, so its own result carries that loop's rounding error (up to ~n·2^-53 of the
+  // variance): the two agree to the digit on the reference's SQL tests and on small values, and may differ by a unit in the last
+  // digit where the variance x 10^6 needs more than the ~16 digits a double holds.  This one is the nearer to the exact value.
+  // No value when n == 0: the reference converts NaN to int64 there, which Go leaves unspecified.  (A decimal field of scale s
+  // stores value * 10^s: its VAR is this one times 10^(-2s); CORR does not depend on the scale.)  Where n·Σx² or (Σx)² does not
+  // fit an __int128 (deep fields with very many rows) the numerator is formed in double instead (moments_var of roaring.py stays
+  // exact there: the two mirrors may differ in that range only).
+  std::optional<int64_t> Var(const std::string& field, const Call* filter = nullptr) {
+    const MomentSums m = Moments(field, nullptr, filter);
+    if (m.n == 0) return std::nullopt;
+    const __int128 cnt = __int128(m.n);
+    __int128 a, b, num;
+    double f;
+    if (__builtin_mul_overflow(cnt, m.sum_xx, &a) || __builtin_mul_overflow(m.sum_x, m.sum_x, &b) || __builtin_sub_overflow(a, b, &num))
+      f = (double(m.n) * double(m.sum_xx) - double(m.sum_x) * double(m.sum_x)) / (double(m.n) * double(m.n));
+    else
+      f = double(num) / (double(m.n) * double(m.n));
+    return int64_t(f * 1e6);
+  }
+  // CORR(fx, fy): the expression of aggregateCorr.Eval (expressionagg.go:1040) in double, in its order of operations, from
+  // the moments converted to double.  No value when n == 0 or when n·Σx² − (Σx)² or its y counterpart is zero (a constant
+  // column): the reference converts NaN or Inf to int64 there, which Go leaves unspecified.
+  std::optional<int64_t> Corr(const std::string& field_x, const std::string& field_y, const Call* filter = nullptr) {
+    const MomentSums m = Moments(field_x, &field_y, filter);
+    if (m.n == 0) return std::nullopt;
+    const double n = double(m.n), sx = double(m.sum_x), sy = double(m.sum_y), sxy = double(m.sum_xy), sxx = double(m.sum_xx), syy = double(m.sum_yy);
+    const double under = (n * sxx - sx * sx) * (n * syy - sy * sy);
+    if (!(under > 0) || std::isinf(under)) return std::nullopt;
+    return int64_t((n * sxy - sx * sy) / std::sqrt(under) * 1e6);
+  }
 
   // ---- Percentile ----------------------------------------------------------------------------
   // executePercentile, executor.go:1310-1595 (integer fields).  Returns false for the "median of
