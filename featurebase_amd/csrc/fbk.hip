@@ -33,6 +33,7 @@
 #include "fbk_moments.hip.h"
 #include "fbk_matrix_cube.hip.h"
 #include "fbk_matrix_distinct.hip.h"
+#include "fbk_matrix_minmax.hip.h"
 #include "fbk_extract.hip.h"
 #include "fbk_sort.hip.h"
 #include "fbk_quantile.hip.h"
@@ -1399,6 +1400,7 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_count_cube_api.inc"
 #include "fbk_group_select_api.inc"
 #include "fbk_matrix_distinct_api.inc"
+#include "fbk_matrix_minmax_api.inc"
 #include "fbk_extract_api.inc"
 #include "fbk_sort_api.inc"
 #include "fbk_quantile_api.inc"

@@ -18,6 +18,7 @@ FBK_E_INVALID, FBK_E_NODEVICE, FBK_E_HIP, FBK_E_NOMEM, FBK_E_CAPACITY, FBK_E_NOT
 TYPE_NIL, TYPE_ARRAY, TYPE_BITMAP, TYPE_RUN = 0, 1, 2, 3
 OP_AND, OP_OR, OP_XOR, OP_ANDNOT = 0, 1, 2, 3
 SORT_DESC, SORT_KEEP_ZERO = 1, 2
+MINMAX_AUTO, MINMAX_DESCENT, MINMAX_SCATTER = 0, 1, 2  # fbk_count_matrix_minmax flags
 RANK_FROM_TOP = 1 << 63
 SETOP_KEEP_BITMAP, SETOP_OPTIMIZE = 0, 1
 QUERY_ACCUMULATE = 1
@@ -192,6 +193,7 @@ SIGNATURES = {
     "fbk_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "fbk_query_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_count_matrix_distinct": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "fbk_count_matrix_minmax": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fbk_count_matrix_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),
     "fbk_count_cube_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),
     "fbk_count_matrix_sum_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),

@@ -1002,6 +1002,22 @@ class Context:
         del keep
         return distinct, counts
 
+    def count_matrix_minmax(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, bit_depth: int,
+                            filt: Optional[Batch] = None, rows_f=None, counts: bool = True, path: int = 0):
+        """GroupBy with Min / Max of an int field per group (SQL MIN(x), MAX(x) ... GROUP BY a, b): for every pair (i, j) the
+        smallest and the largest stored value over A_i ∩ B_j ∩ filt ∩ exists, taken over all the shards together, and how many
+        columns hold each (b = None: the one-field form, one column).  Arguments as count_matrix_sum; path: L.MINMAX_AUTO,
+        _DESCENT (at most 1024 groups) or _SCATTER.  Returns (mins int64, maxs int64, min_counts, max_counts uint64), all
+        [n_a, n_b]; the count arrays are None with counts=False.  An empty group is (INT64_MAX, INT64_MIN, 0, 0); the caller adds Base."""
+        args, keep, n_shards, n_a, n_b = self._msum_args(a, rows_a, b, rows_b, bsi, base_rows, filt, rows_f)
+        mins, maxs = np.zeros((n_a, n_b), dtype=np.int64), np.zeros((n_a, n_b), dtype=np.int64)
+        cmin = np.zeros((n_a, n_b), dtype=np.uint64) if counts else None
+        cmax = np.zeros((n_a, n_b), dtype=np.uint64) if counts else None
+        L.check(self.lib.fbk_count_matrix_minmax(*args, bit_depth, n_shards, path, mins.ctypes.data, maxs.ctypes.data,
+                                                 cmin.ctypes.data if counts else None, cmax.ctypes.data if counts else None))
+        del keep
+        return mins, maxs, cmin, cmax
+
     # -- GroupBy having / sort / offset / limit ---------------------------------------------------
     def _select(self, call, args, sel, has_agg: bool, cap: Optional[int], aggs_slot: bool = True):
         """`call`(*args, sel, out_cells, out_counts[, out_aggs], cap, out_n, out_matched), one retry with the reported size when

@@ -594,6 +594,52 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
                                   const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
                                   uint64_t* out_distinct, uint64_t* out_counts);
 
+/* ---- GroupBy with Min / Max of an int field per group (SQL MIN(x), MAX(x) ... GROUP BY a, b) -----
+ * For every pair (i, j), over ALL the shards given together (X_s = A.rows_a[s*n_a+i] ∩ B.rows_b[s*n_b+j] ∩ F.rows_f[s] ∩ exists,
+ * X = the union of the X_s):
+ *   out_min[i*n_b+j] / out_max[i*n_b+j]    the smallest / largest value over the columns of X
+ *   out_min_counts / out_max_counts        the number of columns of X holding that value.  Pass both or neither as NULL; when
+ *                                          NULL the pass that counts is not run.
+ * The value of a column is fbk_extract_bsi's: sign ? -magnitude : magnitude.  A set sign over magnitude 0 is the value 0; sign and
+ * plane bits outside exists are ignored.  Values are ORDERED as mathematical integers (up to 65 bits at depth 64) and WRITTEN as
+ * int64 with wrap-around, exactly as fbk_bsi_min / fbk_bsi_max write theirs.  Base is not applied: the caller adds it.
+ * An empty group gives out_min = INT64_MAX, out_max = INT64_MIN and counts 0: the identities of the fold, so a merge across nodes
+ * is a plain min / max that adds the counts on equality.  For bit_depth <= 63 a non-empty group always has min <= max, so the
+ * pair itself tells an empty group; at depth 64, where values wrap, ask for the counts.
+ * Relation to the reference: the result is fragment.min / fragment.max (fragment.go:754-853) over the filter Intersect(group
+ * rows, filter) per shard, folded over the shards by ValCount.Smaller / Larger (executor.go:8446-8548).  (The reference's SQL
+ * planner refuses MIN / MAX under GROUP BY: sql3/planner/oppqlgroupby.go:188-195.)  Values are the same while no selected
+ * magnitude reaches 2^63 (the reference's fold compares the wrapped int64).  Counts are the same whenever no column has the sign
+ * bit over magnitude 0: the reference's importers never write that, and its per-shard scan counts such columns apart from the
+ * +0 ones; here they are the value 0 like any other.
+ * Arguments as fbk_count_matrix_sum: b == NULL is the one-field form (n_b must be 1), filter == NULL no filter, bit_depth 0..64,
+ * n_a, n_b <= 4096, row lists [n_shards][n_a], [n_shards][n_b], [n_shards], [n_shards].  n_shards == 0 writes the empty-group
+ * values.  Errors (NULL ctx / a / bsi / base_rows / out_min / out_max, exactly one count pointer NULL, unknown flags, a pinned
+ * descent above its cap, row indexes beyond a batch) are FBK_E_INVALID before any launch.  One synchronisation per call.
+ * flags picks the kernel path:
+ *   FBK_MINMAX_DESCENT  lanes = groups: every group scans the bit planes MSB -> LSB on its own 64-column mask.  Work grows with
+ *                       n_a * n_b whatever the rows hold; at most 1024 groups (FBK_E_INVALID above).
+ *   FBK_MINMAX_SCATTER  lanes = columns: every column updates the groups it is in with 64-bit atomic min / max.  Work is the sum
+ *                       over columns of |A rows holding it| * |B rows holding it|: best for mutex-like fields, poor for set
+ *                       fields with many rows per column.  Device scratch is 48 bytes per group (768 MiB at 4096 x 4096), not
+ *                       tiled.  With counts the operands are walked twice.
+ *   FBK_MINMAX_AUTO     the descent iff n_a * n_b <= 64 (featurebase_amd/csrc/fbk_minmax_plan.h: kMinmaxDescentCells, fixed from a
+ *                       measured sweep on mutex-like rows, where the descent was ahead up to 64 groups at depth 20 and up to 128 at
+ *                       depth 8; a caller whose columns sit in many rows of a field may pin the descent, one with a field of
+ *                       60 bits or more the scatter).
+ * Rows of batches that are not dense are densified a chunk of shards at a time: most = max(1, min(n_shards, 2^30 / per_shard))
+ * with per_shard = 2^17 * (n_a if A is not dense, n_b if B is not, 1 if the filter is not, bit_depth + 2 if the BSI batch is
+ * not); chunk = ceil(n_shards / ceil(n_shards / most)); with more than one chunk the scatter path's counting walk densifies
+ * them again.  The descent path's other scratch is at most 8 MiB of partials and 64 bytes per group. */
+#define FBK_MINMAX_AUTO    0u  /* the library chooses the kernel path by the shape */
+#define FBK_MINMAX_DESCENT 1u  /* pin the plane-descent path; FBK_E_INVALID when n_a * n_b exceeds its cap */
+#define FBK_MINMAX_SCATTER 2u  /* pin the per-column scatter path */
+int32_t fbk_count_matrix_minmax(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
+                                const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
+                                const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
+                                uint32_t flags, int64_t* out_min, int64_t* out_max, uint64_t* out_min_counts,
+                                uint64_t* out_max_counts);
+
 /* ---- GroupBy(..., having=, sort=, offset=, limit=): only the selected groups leave the device -----
  * executeGroupBy's tail (executor.go:3176-3459: ApplyConditionToGroupCounts / satisfiesCondition :3787-3916, groupCountSorter and
  * getSorter :3096-3162, sort.Stable :3409, applyLimitAndOffsetToGroupByResult :3441-3459) applied to the totals of a GroupBy call

@@ -48,6 +48,15 @@ struct GroupCount {  // executor.go GroupCount
   int64_t Agg = 0;
   bool operator==(const GroupCount& o) const { return Group == o.Group && Count == o.Count && Agg == o.Agg; }
 };
+struct GroupMinMax {  // a GroupBy record with the Min / Max of an int field (SQL MIN(x), MAX(x) ... GROUP BY): Executor::GroupByMinMax
+  std::vector<FieldRow> Group;
+  uint64_t Count = 0;                   // |group ∩ filter|, as GroupBy's
+  int64_t Min = 0, Max = 0;             // Base added; (0, 0) when no column of the group has a value
+  uint64_t MinCount = 0, MaxCount = 0;  // the columns holding Min / Max; 0: no column of the group has a value
+  bool operator==(const GroupMinMax& o) const {
+    return Group == o.Group && Count == o.Count && Min == o.Min && Max == o.Max && MinCount == o.MinCount && MaxCount == o.MaxCount;
+  }
+};
 struct GroupByCondition {  // having=Condition(count|sum <op> v): satisfiesCondition (executor.go:3787-3901)
   std::string subject;    // "count" | "sum"
   uint32_t op = 0;        // FBK_HAVING_*
@@ -977,6 +986,28 @@ class Executor {
     return out;
   }
 
+  // GroupBy(Rows(f0), Rows(f1), ..., filter) with the Min and the Max of an int field per group — what SQL's
+  // SELECT f0, f1, MIN(x), MAX(x) ... GROUP BY f0, f1 asks for (the reference's planner refuses it: sql3/planner/oppqlgroupby.go:188-195).
+  // The groups are GroupBy's (Count = |group ∩ filter|, Count == 0 skipped, odometer order, limit); Min / Max = the smallest /
+  // largest value of the field over group ∩ filter, Base added, with the number of columns holding each (fragment.min / .max per
+  // shard folded by ValCount.Smaller / Larger, executor.go:8446-8548).  The last one or two levels take one
+  // fbk_count_matrix_minmax call per block of kSumBlock x kSumBlock rows; earlier levels fix their row (prefix ∩ row) as
+  // GroupByCountDistinct does.
+  std::vector<GroupMinMax> GroupByMinMax(const std::vector<std::string>& fields, const Call* filter, const std::string& agg_field, uint64_t limit = 0) {
+    if (fields.empty()) throw Error(FBK_E_INVALID, "need at least one child call");  // executor.go:3927
+    if (!idx_.ints_.count(agg_field))
+      throw Error(FBK_E_INVALID, "GroupBy Min / Max(field=" + agg_field + "): " +
+                                     (idx_.sets_.count(agg_field) ? "set fields are not supported, only int fields" : "no such int field"));
+    Scope sc(*this, {filter});
+    std::vector<GroupMinMax> out;
+    if (shards().empty()) return out;
+    std::unique_ptr<RowSet> prefix;
+    if (filter) prefix.reset(new RowSet(eval(*filter)));
+    std::vector<FieldRow> group;
+    minmax_rec(fields, 0, prefix.get(), agg_field, limit, group, out);
+    return out;
+  }
+
   // ---- Extract --------------------------------------------------------------------------------
   // Extract(Limit(filter, limit=, offset=), Rows(f0), Rows(f1), ...) (executeExtract, executor.go:4711-5046; executeLimitCall,
   // :1027-1100): the filter's columns in ascending order, offset then limit, and per column one entry per field:
@@ -1565,6 +1596,100 @@ class Executor {
         for (size_t i = 0; i < bi; ++i)
           for (size_t j = 0; j < bj; ++j) distinct[(i0 + i) * nb + j0 + j] = int64_t(d[i * bj + j]);
       }
+  }
+  // Min / Max of an int field for the last level (fb == nullptr) or the last two levels: fbk_count_matrix_minmax with the prefix
+  // row (if any) as the filter, in blocks of kSumBlock x kSumBlock rows as sum_matrix.  Base is added where the group has a value.
+  void minmax_matrix(const std::string& agg_field, const Index::SetField& fa, const std::vector<uint32_t>& rows_a, const Index::SetField* fb,
+                     const std::vector<uint32_t>* rows_b, const RowSet* prefix, std::vector<int64_t>& mins, std::vector<int64_t>& maxs,
+                     std::vector<uint64_t>& cmin, std::vector<uint64_t>& cmax) {
+    const Index::IntField& f = idx_.ints_.at(agg_field);
+    std::vector<uint32_t> base = base_rows(f);
+    const size_t n = base.size(), na = fa.row_ids.size(), nb = fb ? fb->row_ids.size() : 1;
+    mins.assign(na * nb, 0), maxs.assign(na * nb, 0), cmin.assign(na * nb, 0), cmax.assign(na * nb, 0);
+    for (size_t i0 = 0; i0 < na; i0 += kSumBlock)
+      for (size_t j0 = 0; j0 < nb; j0 += kSumBlock) {
+        const size_t bi = std::min(kSumBlock, na - i0), bj = std::min(kSumBlock, nb - j0);
+        const std::vector<uint32_t> ra = row_block(rows_a, n, na, i0, bi);
+        const std::vector<uint32_t> rb = fb ? row_block(*rows_b, n, nb, j0, bj) : std::vector<uint32_t>();
+        std::vector<int64_t> mn(bi * bj), mx(bi * bj);
+        std::vector<uint64_t> c0(bi * bj), c1(bi * bj);
+        check(fbk_count_matrix_minmax(idx_.ctx_, fa.batch, ra.data(), uint32_t(bi), fb ? fb->batch : nullptr, fb ? rb.data() : nullptr, uint32_t(bj),
+                                      prefix ? prefix->batch() : nullptr, prefix ? prefix->rows().data() : nullptr, f.batch, base.data(), f.bit_depth,
+                                      uint32_t(n), FBK_MINMAX_AUTO, mn.data(), mx.data(), c0.data(), c1.data()));
+        for (size_t i = 0; i < bi; ++i)
+          for (size_t j = 0; j < bj; ++j) {
+            const size_t k = (i0 + i) * nb + j0 + j, q = i * bj + j;
+            if (!c0[q]) continue;  // an empty group: (0, 0) with counts 0
+            mins[k] = int64_t(uint64_t(mn[q]) + uint64_t(f.base)), maxs[k] = int64_t(uint64_t(mx[q]) + uint64_t(f.base));
+            cmin[k] = c0[q], cmax[k] = c1[q];
+          }
+      }
+  }
+  // GroupByMinMax over fields[level..]: the last one or two levels are one count call and one minmax_matrix; earlier levels
+  // materialise prefix ∩ row as group_by_rec does
+  bool minmax_rec(const std::vector<std::string>& fields, size_t level, const RowSet* prefix, const std::string& agg_field, uint64_t limit,
+                  std::vector<FieldRow>& group, std::vector<GroupMinMax>& out) {
+    const size_t n = shards().size();
+    const Index::SetField& fa = idx_.sets_.at(fields[level]);
+    const size_t na = fa.row_ids.size();
+    if (na == 0) return true;
+    const size_t remaining = fields.size() - level;
+    if (remaining > 2) {
+      for (size_t i = 0; i < na; ++i) {
+        RowSet r = leaf_row(fields[level], fa.row_ids[i]);
+        group.push_back({fields[level], fa.row_ids[i]});
+        bool go;
+        if (prefix) {
+          RowSet p = setop(FBK_OP_AND, r, *prefix);
+          go = count_rows(p) == 0 ? true : minmax_rec(fields, level + 1, &p, agg_field, limit, group, out);
+        } else {
+          go = minmax_rec(fields, level + 1, &r, agg_field, limit, group, out);
+        }
+        group.pop_back();
+        if (!go) return false;
+      }
+      return true;
+    }
+    const Index::SetField* fb = remaining == 2 ? &idx_.sets_.at(fields[level + 1]) : nullptr;
+    const size_t nb = fb ? fb->row_ids.size() : 1;
+    if (nb == 0) return true;
+    const std::vector<uint32_t> rows_a = field_rows(fa), rows_b = fb ? field_rows(*fb) : std::vector<uint32_t>();
+    std::vector<uint64_t> tot(na * nb, 0);  // Count: |group ∩ prefix|
+    if (fb) {
+      for (size_t i0 = 0; i0 < na; i0 += kSumBlock)
+        for (size_t j0 = 0; j0 < nb; j0 += kSumBlock) {
+          const size_t bi = std::min(kSumBlock, na - i0), bj = std::min(kSumBlock, nb - j0);
+          const std::vector<uint32_t> ra = row_block(rows_a, n, na, i0, bi), rb = row_block(rows_b, n, nb, j0, bj);
+          std::vector<uint64_t> c(bi * bj);
+          check(fbk_count_matrix(idx_.ctx_, fa.batch, ra.data(), uint32_t(bi), fb->batch, rb.data(), uint32_t(bj), prefix ? prefix->batch() : nullptr,
+                                 prefix ? prefix->rows().data() : nullptr, uint32_t(n), c.data(), nullptr));
+          for (size_t i = 0; i < bi; ++i) std::copy(c.begin() + i * bj, c.begin() + (i + 1) * bj, tot.begin() + (i0 + i) * nb + j0);
+        }
+    } else if (prefix) {
+      check(fbk_count_matrix(idx_.ctx_, fa.batch, rows_a.data(), uint32_t(na), prefix->batch(), prefix->rows().data(), 1, nullptr, nullptr, uint32_t(n),
+                             tot.data(), nullptr));
+    } else {
+      std::vector<uint64_t> c(n * na);
+      check(fbk_count(idx_.ctx_, fa.batch, rows_a.data(), c.size(), c.data()));
+      for (size_t s = 0; s < n; ++s)
+        for (size_t i = 0; i < na; ++i) tot[i] += c[s * na + i];
+    }
+    std::vector<int64_t> mins, maxs;
+    std::vector<uint64_t> cmin, cmax;
+    minmax_matrix(agg_field, fa, rows_a, fb, fb ? &rows_b : nullptr, prefix, mins, maxs, cmin, cmax);
+    for (size_t i = 0; i < na; ++i)
+      for (size_t j = 0; j < nb; ++j) {
+        const size_t k = i * nb + j;
+        if (!tot[k]) continue;  // groupByIterator.Next skips Count == 0 (executor.go:8905-8913)
+        GroupMinMax g;
+        g.Group = group;
+        g.Group.push_back({fields[level], fa.row_ids[i]});
+        if (fb) g.Group.push_back({fields[level + 1], fb->row_ids[j]});
+        g.Count = tot[k], g.Min = mins[k], g.Max = maxs[k], g.MinCount = cmin[k], g.MaxCount = cmax[k];
+        out.push_back(std::move(g));
+        if (limit && out.size() >= limit) return false;
+      }
+    return true;
   }
   // fields[level..]: the last three levels are one count-cube call; with an aggregate the last two are one count-matrix-sum /
   // -distinct call; earlier levels materialise prefix ∩ row (gbi.rows[i].row.Intersect(gbi.rows[i-1].row), executor.go:8829-8834)
