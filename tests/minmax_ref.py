@@ -98,6 +98,60 @@ def numpy_expected(A: np.ndarray, Bw: Optional[np.ndarray], F: Optional[np.ndarr
     return mins, maxs, cmin, cmax
 
 
+# ---- a call of 19 shards over 5 stored ones (tests/test_gpu_count_matrix_minmax.py: launches that go round their loops) -----------
+# Shard s reads the set-field and filter rows of stored shard MANY_ROWS[s] and the fragment MANY_FRAG[s].  Fragments 0 .. 2 lack
+# their top 3, 2, 1 planes and serve the first 8 shards only (one round of the grid of k_minmax_scatter / _holders and of a one-tile
+# k_minmax_descent); fragments 3 and 4 have every plane and serve shards 8 .. 18 in ten different pairings with the stored rows (shard
+# 18 repeats shard 8).  So the extremes of a group lie beyond the first round, and a shard that a later round skipped or read twice
+# shows in the values or, where another shard holds the same extreme, in the counts.
+MANY_SHARDS, MANY_STORED = 19, 5
+MANY_ROWS = [s % MANY_STORED for s in range(MANY_SHARDS)]
+MANY_FRAG = [0, 1, 2, 0, 1, 2, 0, 1] + [3, 4] * 5 + [3]
+
+
+def many_shard_case(n_a: int, n_b: Optional[int], depth: int):
+    """the stored words (A [5, n_a, 16, 1024], Bw [5, n_b, 16, 1024] or None with n_b None: the one-field form, F [5, 16, 1024],
+    S [5, depth + 2, 16, 1024]): random rows, exists one column in 128, sign and plane bits also outside exists"""
+    import datagen as D
+
+    rng = D.rng_for(8950, n_a, n_b or 0, depth)
+
+    def rnd(shape, ands=0):
+        w = rng.integers(0, 1 << 63, shape, dtype=np.uint64) * 2 + rng.integers(0, 2, shape, dtype=np.uint64)
+        for _ in range(ands):
+            w &= rng.integers(0, 1 << 63, shape, dtype=np.uint64) * 2 + rng.integers(0, 2, shape, dtype=np.uint64)
+        return w
+
+    A = rnd((MANY_STORED, n_a, 16, 1024))
+    Bw = rnd((MANY_STORED, n_b, 16, 1024)) if n_b else None
+    F = rnd((MANY_STORED, 16, 1024))
+    S = rnd((MANY_STORED, depth + 2, 16, 1024))
+    S[:, 0] &= rnd((MANY_STORED, 16, 1024), 6)
+    A[0, 0, 3] = 0  # an empty container in a row
+    for k in range(3):
+        S[k, 2 + depth - (3 - k):] = 0
+    # fragments 3 and 4: a column whose top 9 planes are all set gets every plane set (about 16 columns of a fragment's 8192).  The
+    # largest magnitude then sits on several columns of every later shard, and a group's tie count takes part from each of them
+    top = min(9, depth)
+    S[3:, 2:2 + depth - top] |= np.bitwise_and.reduce(S[3:, 2 + depth - top:2 + depth], axis=1)[:, None]
+    return A, Bw, F, S
+
+
+def many_shard_lists(n_a: int, n_b: Optional[int], depth: int):
+    """(rows_a [19, n_a], rows_b [19, n_b] or None, rows_f [19], base_rows [19]) into dense uploads of many_shard_case's words"""
+    rows, frag = np.array(MANY_ROWS, dtype=np.uint32), np.array(MANY_FRAG, dtype=np.uint32)
+    ra = rows[:, None] * np.uint32(n_a) + np.arange(n_a, dtype=np.uint32)[None, :]
+    rb = rows[:, None] * np.uint32(n_b) + np.arange(n_b, dtype=np.uint32)[None, :] if n_b else None
+    return ra, rb, rows.copy(), frag * np.uint32(depth + 2)
+
+
+def many_shard_words(A, Bw, F, S, shards: Optional[Sequence[int]] = None):
+    """the words the given shards of the call read (all 19: None), as numpy_expected takes them"""
+    sh = list(range(MANY_SHARDS)) if shards is None else list(shards)
+    r, f = [MANY_ROWS[s] for s in sh], [MANY_FRAG[s] for s in sh]
+    return A[r], (Bw[r] if Bw is not None else None), F[r], S[f]
+
+
 def smaller(a: Tuple[int, int], b: Tuple[int, int]) -> Tuple[int, int]:
     """ValCount.Smaller (executor.go:8446-8468) on (Val, Count)"""
     if a[1] == 0 or (b[0] < a[0] and b[1] > 0):

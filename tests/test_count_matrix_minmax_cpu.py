@@ -176,3 +176,62 @@ def test_numpy_orders_65_bit_values_at_depth_64():
     mn, mx, c0, c1 = M.numpy_expected(A, None, None, S, 64)
     assert mn[:, 0].tolist() == [1, 3] and mx[:, 0].tolist() == [M.INT64_MIN + 1, M.INT64_MIN + 1]
     assert c0[:, 0].tolist() == [1, 1] and c1[:, 0].tolist() == [1, 1]
+
+
+def test_nineteen_shards_take_every_kernel_round_its_loop():
+    """what tests/test_gpu_count_matrix_minmax.py's 19-shard cases rest on: k_minmax_scatter / _holders run min(ceil(ns * 1024 / 4),
+    2048) blocks of four units, the descent descent_grid() blocks per tile"""
+    n = M.MANY_SHARDS
+    assert min(-(-n * 1024 // 4), 2048) * 4 == 8 * 1024 and n > 2 * 8  # the scatter: 8 shards a round, two whole rounds and a part
+    grid = lambda cells: tuple(M.plan_check(["G %d %d" % (n, cells)])[0])  # noqa: E731  (tiles, unit blocks)
+    assert grid(5 * 7) == (1, 2048) and grid(13 * 11) == (3, 682) and grid(70) == (2, 1024)
+    assert (682 * 4) % 1024 != 0 and 682 % 64 != 0 and -(-n * 1024 // (682 * 4)) == 8  # steps of 2 or 3 shards, 8 rounds (the last a part)
+    steps = {(r + 1) * 2728 // 1024 - r * 2728 // 1024 for r in range(7)}
+    assert steps == {2, 3}
+    cells, cap = M.plan_constants()
+    assert 5 * 7 <= cells < 70 <= 13 * 11 <= cap < 33 * 65 and -(-65 // 64) == 2
+    assert len(M.MANY_ROWS) == len(M.MANY_FRAG) == n and set(M.MANY_FRAG[:8]) == {0, 1, 2} and set(M.MANY_FRAG[8:]) == {3, 4}
+    pairs = list(zip(M.MANY_ROWS, M.MANY_FRAG))
+    assert len(set(pairs)) == n - 1 and pairs[18] == pairs[8]
+
+
+def _fold(parts, keep):
+    """per-shard results -> the call's over the shards `keep` (depth <= 63: the written int64 is the value)"""
+    mn = np.min([parts[s][0] for s in keep], axis=0)
+    mx = np.max([parts[s][1] for s in keep], axis=0)
+    c0 = np.sum([np.where(parts[s][0] == mn, parts[s][2], 0) for s in keep], axis=0, dtype=np.uint64)
+    c1 = np.sum([np.where(parts[s][1] == mx, parts[s][3], 0) for s in keep], axis=0, dtype=np.uint64)
+    return mn, mx, c0, c1
+
+
+@pytest.mark.parametrize("with_filter", [False, True])
+@pytest.mark.parametrize("depth", [7, 20])
+@pytest.mark.parametrize("shape", [(5, 7), (13, 11), (33, 65), (70, None)])
+def test_nineteen_shard_cases_tell_a_shard_lost_beyond_the_first_round(shape, depth, with_filter):
+    """a condition on the inputs of the GPU test, checked with the reference alone: the result over shards [0, 8) differs from the
+    full one in the minimum and in the maximum of at least a quarter of the non-empty groups, and the result without any one of
+    the shards 8 .. 18 differs from the full one in the counts"""
+    n_a, n_b = shape
+    A, Bw, F, S = M.many_shard_case(n_a, n_b, depth)
+    one = {}  # the shards that read the same rows and fragment share a result
+    for s in range(M.MANY_SHARDS):
+        key = (M.MANY_ROWS[s], M.MANY_FRAG[s])
+        if key not in one:
+            a, b, f, sw = M.many_shard_words(A, Bw, F, S, [s])
+            one[key] = M.numpy_expected(a, b, f if with_filter else None, sw, depth)
+    parts = [one[(M.MANY_ROWS[s], M.MANY_FRAG[s])] for s in range(M.MANY_SHARDS)]
+    every = list(range(M.MANY_SHARDS))
+    full = _fold(parts, every)
+    if shape == (5, 7):  # the fold of the per-shard results is the reference over all the words at once
+        a, b, f, sw = M.many_shard_words(A, Bw, F, S)
+        for x, y in zip(full, M.numpy_expected(a, b, f if with_filter else None, sw, depth)):
+            assert x.dtype == y.dtype and np.array_equal(x, y)
+    held = full[2] > 0
+    assert held.sum() * 2 > held.size and (full[0][held] < 0).all() and (full[1][held] > 0).all()
+    first = _fold(parts, every[:8])
+    assert ((first[0] != full[0]) & held).sum() * 4 >= held.sum() and ((first[1] != full[1]) & held).sum() * 4 >= held.sum()
+    for s in range(8, M.MANY_SHARDS):
+        without = _fold(parts, [t for t in every if t != s])
+        assert not (np.array_equal(without[2], full[2]) and np.array_equal(without[3], full[3])), ("shard", s)
+    # the tie counts differ from group to group: a result written to another group's place shows
+    assert np.unique(full[2][held]).size > 3 and np.unique(full[3][held]).size > 3

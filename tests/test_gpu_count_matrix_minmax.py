@@ -3,7 +3,8 @@
 brute force for every pair (tests/minmax_ref.py); where the data has neither a sign bit over magnitude 0 nor a magnitude of 2^63
 or more, sampled pairs are also checked against the reference's composition (the CPU test shows the two agree there).  Dense
 batches over shard counts, shapes on both sides of the path rule and depths 0..64; mutex-like rows with few distinct values;
-counts=False; the one-field form; encoded batches (the densify path); calls that densify in more than one chunk; the row-list
+counts=False; the one-field form; encoded batches (the densify path); calls that densify in more than one chunk; 19 shards, at
+which every kernel goes round its grid-stride loop more than once (by steps that are no whole number of shards, too); the row-list
 limits; recovery after an error."""
 import numpy as np
 import pytest
@@ -45,10 +46,10 @@ def _all_paths(ctx, plan, n_cells, *args, counts=True, **kw):
     return got[AUTO]
 
 
-def _equal(got, exp, counts=True):
+def _equal(got, exp, counts=True, what=()):
     for k, name in enumerate(("mins", "maxs", "min_counts", "max_counts")[: 4 if counts else 2]):
         bad = np.argwhere(got[k] != exp[k])
-        assert bad.size == 0, (name, bad[:4].tolist(), got[k][tuple(bad[0])], exp[k][tuple(bad[0])])
+        assert bad.size == 0, what + (name, bad[:4].tolist(), got[k][tuple(bad[0])], exp[k][tuple(bad[0])])
 
 
 def _clean(S, depth):
@@ -259,6 +260,38 @@ def test_densify_in_several_chunks(gpu_ctx, oracle, B, plan, n_sh, n_a, two_fiel
     finally:
         for b in (bA, bB, bF, bS):
             b.free()
+
+
+# 19 shards: on one tile two whole rounds of 8 shards of either kernel's grid and a partial one.  (5, 7): one tile, the descent
+# steps by exactly 8 shards and the scatter by 8192 units.  (13, 11): 3 tiles, the descent's grid is 682 blocks = 2728 units a step,
+# no multiple of a shard's 1024, so the steps advance by 2 or 3 shards, and k_minmax_fold gets 682 partials.  (33, 65): above the
+# descent's cap, two words of B rows.  (70, None): the one-field form, two tiles.  tests/test_count_matrix_minmax_cpu.py shows what
+# these numbers rest on, and that the data tells a shard skipped beyond the first round.
+MANY_SHARD_CASES = [((5, 7), (AUTO, DESCENT, SCATTER)), ((13, 11), (DESCENT, SCATTER)), ((33, 65), (AUTO, SCATTER)), ((70, None), (AUTO, DESCENT, SCATTER))]
+
+
+@pytest.mark.parametrize("with_filter", [False, True])
+@pytest.mark.parametrize("depth", [7, 20])
+@pytest.mark.parametrize("shape,pins", MANY_SHARD_CASES)
+def test_launches_that_go_round_their_loops(gpu_ctx, plan, shape, pins, depth, with_filter):
+    n_a, n_b = shape
+    assert DESCENT not in pins or n_a * (n_b or 1) <= plan[1]
+    A, Bw, F, S = M.many_shard_case(n_a, n_b, depth)
+    bA, _, bB, _, bF, _, bS, _ = T._upload_dense(gpu_ctx, A, Bw, F, S)
+    ra, rb, rf, base = M.many_shard_lists(n_a, n_b, depth)
+    try:
+        gA, gB, gF, gS = M.many_shard_words(A, Bw, F, S)
+        exp = M.numpy_expected(gA, gB, gF if with_filter else None, gS, depth)
+        assert (exp[2] > 0).sum() * 2 > exp[2].size
+        for p in pins:
+            for counts in (True, False):
+                got = gpu_ctx.count_matrix_minmax(bA, ra, bB, rb, bS, base, depth, bF if with_filter else None, rf if with_filter else None, counts=counts, path=p)
+                assert counts or (got[2] is None and got[3] is None)
+                _equal(got, exp, counts=counts, what=("path", p, "counts", counts))
+    finally:
+        for b in (bA, bB, bF, bS):
+            if b is not None:
+                b.free()
 
 
 def test_row_list_limits(gpu_ctx, plan):

@@ -1,6 +1,7 @@
 """Structural fuzz of the calls that read their operands through the shared dense-operand walk (DenseOperands): fbk_bsi_sort and
 fbk_extract_open_columns, fbk_extract_open / _span / _columns / _bsi / _rows, fbk_bsi_quantiles / _percentile, fbk_count_matrix_sum and
-its prepared form, fbk_count_matrix_distinct, fbk_bsi_distinct_rows and fbk_bsi_distinct.  The per-operator tests are thorough on
+its prepared form, fbk_count_matrix_distinct, fbk_bsi_distinct_rows and fbk_bsi_distinct, fbk_count_matrix_minmax under every path
+pin with and without counts, fbk_bsi_moments and fbk_count_cube.  The per-operator tests are thorough on
 values and regular on structure; this file is the other way round.  tests/fuzz_ops_gen.py makes the cases (a pool of rows of every
 container archetype uploaded twice, encoded and dense; arbitrary row lists into it; every operand draws its batch) and the
 expectations (the numpy references); tests/test_fuzz_ops_cpu.py checks both without a GPU.  Everything is integer and bit-exact.
@@ -16,6 +17,7 @@ import pytest
 import distinct_rows_ref as DR
 import extract_ref as X
 import fuzz_ops_gen as G
+import minmax_ref as MM
 import pct_ref as P
 import sort_ref as SR
 from featurebase_amd import lib as L
@@ -254,6 +256,93 @@ def test_fuzz_distinct_rows(gpu_ctx, oracle, it):
         up.free()
 
 
+MINMAX_OUT = ("mins", "maxs", "min_counts", "max_counts")
+MINMAX_PINS = {"auto": L.MINMAX_AUTO, "descent": L.MINMAX_DESCENT, "scatter": L.MINMAX_SCATTER}
+
+
+def _minmax_equal(got, exp, counts, what):
+    """bit for bit, every output; the message names the first differing group"""
+    for k, name in enumerate(MINMAX_OUT):
+        if k >= 2 and not counts:
+            assert got[k] is None, what
+            continue
+        bad = np.argwhere(got[k] != exp[k])
+        assert got[k].dtype == exp[k].dtype and bad.size == 0, (what, name, "group", bad[0].tolist(), "got", got[k][tuple(bad[0])], "expected", exp[k][tuple(bad[0])])
+
+
+def _minmax_pins(n_cells, _cap=[]):
+    """every path pin the shape admits: the descent up to kMinmaxDescentMaxCells groups"""
+    if not _cap:
+        _cap.append(MM.plan_constants()[1])
+    return [p for p in ("auto", "descent", "scatter") if p != "descent" or n_cells <= _cap[0]]
+
+
+@pytest.mark.parametrize("it", range(ITERS))
+def test_fuzz_groupby_minmax(gpu_ctx, it):
+    """The identity of the all-ones row and column: the group is the filter alone, fbk_bsi_min / fbk_bsi_max per shard folded by
+    ValCount.Smaller / Larger.  Those calls order the wrapped int64, so the identity is compared while no selected magnitude reaches
+    2^63; and they count a sign bit over magnitude 0 apart from +0 (include/fbk.h, fbk_count_matrix_minmax), which changes the counts
+    and never the values: the counts are compared where no selected column has one.  tests/test_fuzz_ops_cpu.py shows that the
+    default iterations leave cases of either kind."""
+    c = G.Case("groupby_minmax", it)
+    up = Uploaded(gpu_ctx, c)
+    try:
+        args = _groupby_args(up, c)
+        exp = c.minmax_expected()
+        for pin in _minmax_pins(c.n_a * c.n_b):
+            for counts in (True, False):
+                got = gpu_ctx.count_matrix_minmax(*args, counts=counts, path=MINMAX_PINS[pin])
+                _minmax_equal(got, exp, counts, (c, "path", pin, "counts", counts))
+        held = c.group_counts() > 0  # a group holds a value exactly where GroupBy Sum's reference counts a column
+        assert np.array_equal(exp[2] > 0, held) and np.array_equal(exp[3] > 0, held), c
+        mag, sign = c.selected_magnitudes
+        if mag.size == 0 or int(mag.max()) < 1 << 63:
+            fa = filter_args(up, c)
+            lo, hi = (0, 0), (0, 0)
+            for v, n in zip(*gpu_ctx.bsi_min(up.of("bsi"), c.base_rows, c.depth, *fa)):
+                lo = MM.smaller(lo, (int(v), int(n)))
+            for v, n in zip(*gpu_ctx.bsi_max(up.of("bsi"), c.base_rows, c.depth, *fa)):
+                hi = MM.larger(hi, (int(v), int(n)))
+            mn, mx, n0, n1 = (int(e[c.i_full, c.j_full]) for e in exp)
+            assert (lo[1] > 0, hi[1] > 0) == (n0 > 0, n1 > 0) and (n0 == 0 or (lo[0], hi[0]) == (mn, mx)), (c, lo, hi, mn, mx, n0, n1)
+            if not (sign & (mag == 0)).any():
+                assert (lo[1], hi[1]) == (n0, n1), (c, lo, hi, n0, n1)
+    finally:
+        up.free()
+
+
+@pytest.mark.parametrize("it", range(ITERS))
+def test_fuzz_moments(gpu_ctx, it):
+    c = G.Case("moments", it)
+    up = Uploaded(gpu_ctx, c)
+    try:
+        y = (up.of("y"), c.base_rows_y, c.depth_y) if c.base_rows_y is not None else (None, None, 0)
+        got = gpu_ctx.bsi_moments(up.of("bsi"), c.base_rows, c.depth, *y, *filter_args(up, c))
+        exp = c.moments_expected()
+        assert exp.n == c.total, c
+        for name, g, e in zip(exp._fields, got, exp):
+            assert int(g) == e, (c, name, int(g), e)
+    finally:
+        up.free()
+
+
+@pytest.mark.parametrize("it", range(ITERS))
+def test_fuzz_groupby_cube(gpu_ctx, it):
+    c = G.Case("groupby_cube", it)
+    up = Uploaded(gpu_ctx, c)
+    try:
+        fa = filter_args(up, c)
+        got = gpu_ctx.count_cube(up.of("p"), c.rows_p, up.of("a"), c.rows_a, up.of("b"), c.rows_b, *fa)
+        exp = c.cube_expected()
+        bad = np.argwhere(got != exp)
+        assert got.shape == exp.shape and bad.size == 0, (c, "cell", bad[0].tolist(), got[tuple(bad[0])], exp[tuple(bad[0])])
+        # the all-ones row of P: the count matrix of A x B under the same filter; with the all-ones rows of A and B: the filter's count
+        assert np.array_equal(got[c.p_full], gpu_ctx.count_matrix(up.of("a"), c.rows_a, up.of("b"), c.rows_b, *fa)), c
+        assert int(got[c.p_full, c.i_full, c.j_full]) == c.total, c
+    finally:
+        up.free()
+
+
 # ---- a shorter last chunk, one call per walk ------------------------------------------------------------------------------------
 class ShortUploaded:
     def __init__(self, ctx, sc, names):
@@ -382,5 +471,48 @@ def test_short_last_chunk_groupby_distinct(gpu_ctx):
         _, ec, ed = sc.groupby()
         dist, counts = gpu_ctx.count_matrix_distinct(up.b["a"], sc.rows_a, up.b["b"], sc.rows_b, up.b["bsi"], sc.base_rows, sc.depth, up.b["filter"], sc.rows_f)
         assert int(ed.sum()) > 100 and np.array_equal(counts, ec) and np.array_equal(dist, ed), sc.chunks
+    finally:
+        up.free()
+
+
+def test_short_last_chunk_groupby_minmax(gpu_ctx):
+    """65 shards as 33 + 32 and 61 groups: AUTO (the descent), the descent and the scatter pinned, with counts; a chunk of 33 shards
+    is also more than a round of either kernel's grid, and the scatter's counting walk densifies the uneven chunks once more"""
+    sc = G.ShortCase("groupby_minmax")
+    up = ShortUploaded(gpu_ctx, sc, ("a", "b", "bsi", "filter"))
+    try:
+        exp = sc.groupby(minmax=True)
+        assert int((exp[2] > 0).sum()) > 20 and ((exp[0] < exp[1]) & (exp[2] > 0)).any(), sc.chunks
+        for pin in _minmax_pins(sc.n_a * sc.n_b):
+            got = gpu_ctx.count_matrix_minmax(up.b["a"], sc.rows_a, up.b["b"], sc.rows_b, up.b["bsi"], sc.base_rows, sc.depth, up.b["filter"], sc.rows_f,
+                                              path=MINMAX_PINS[pin])
+            _minmax_equal(got, exp, True, (sc.chunks, "path", pin))
+    finally:
+        up.free()
+
+
+@pytest.mark.parametrize("name", ["moments", "moments_dense_y"])
+def test_short_last_chunk_moments(gpu_ctx, name):
+    sc = G.ShortCase(name)
+    up = ShortUploaded(gpu_ctx, sc, ("bsi", "y", "filter"))
+    try:
+        got = gpu_ctx.bsi_moments(up.b["bsi"], sc.base_rows, sc.depth, up.b["y"], sc.base_rows_y, sc.depth, up.b["filter"], sc.rows_f)
+        exp = sc.moments()
+        assert exp.n > 100 and tuple(int(g) for g in got) == tuple(exp), (name, sc.chunks, tuple(got), exp)
+        if name == "moments":  # the one-field form over the same row lists (R = 67: one chunk)
+            got = gpu_ctx.bsi_moments(up.b["bsi"], sc.base_rows, sc.depth, filt=up.b["filter"], rows_f=sc.rows_f)
+            assert tuple(int(g) for g in got) == tuple(sc.moments(one_field=True)), (name, "one field")
+    finally:
+        up.free()
+
+
+def test_short_last_chunk_groupby_cube(gpu_ctx):
+    sc = G.ShortCase("groupby_cube")
+    up = ShortUploaded(gpu_ctx, sc, ("p", "a", "b", "filter"))
+    try:
+        got = gpu_ctx.count_cube(up.b["p"], sc.rows_p, up.b["a"], sc.rows_a, up.b["b"], sc.rows_b, up.b["filter"], sc.rows_f)
+        exp = sc.cube()
+        bad = np.argwhere(got != exp)
+        assert int((exp > 0).sum()) > 1000 and bad.size == 0, (sc.chunks, "cell", bad[0].tolist(), got[tuple(bad[0])], exp[tuple(bad[0])])
     finally:
         up.free()

@@ -7,7 +7,7 @@ re-rolls them (scripts/fuzz_parity.sh).
 
 The rest of the entry points are fuzzed in
   tests/test_gpu_fuzz_ops.py  the calls that read densified operands: Sort, Extract, Quantiles / Percentile, GroupBy Sum and
-                              Count(Distinct), Distinct rows; and their walks with a shorter last chunk
+                              Count(Distinct) / Min-Max, moments, the cube, Distinct rows; and their walks with a shorter last chunk
   tests/fuzz_ops_gen.py       its case generator and expectations (no GPU)
   tests/test_fuzz_ops_cpu.py  the generator and the references checked against each other (no GPU)
   tests/test_gpu_fuzz_prepared.py  the prepared forms (fbk_query_*, fbk_plan_*): schedules of runs, reads, rewritten and compacted inputs,
