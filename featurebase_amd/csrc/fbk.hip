@@ -31,6 +31,7 @@
 #include "fbk_matrix_fusedq.hip.h"
 #include "fbk_matrix_sum.hip.h"
 #include "fbk_moments.hip.h"
+#include "fbk_compare.hip.h"
 #include "fbk_matrix_cube.hip.h"
 #include "fbk_matrix_distinct.hip.h"
 #include "fbk_matrix_minmax.hip.h"
@@ -1397,6 +1398,7 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_count_matrix_api.inc"  // the GroupBy count matrix: MatrixPlan; its rules: fbk_count_matrix_plan.h
 #include "fbk_matrix_sum_api.inc"
 #include "fbk_moments_api.inc"
+#include "fbk_compare_api.inc"
 #include "fbk_count_cube_api.inc"
 #include "fbk_group_select_api.inc"
 #include "fbk_matrix_distinct_api.inc"

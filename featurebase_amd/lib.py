@@ -21,6 +21,7 @@ SORT_DESC, SORT_KEEP_ZERO = 1, 2
 MINMAX_AUTO, MINMAX_DESCENT, MINMAX_SCATTER = 0, 1, 2  # fbk_count_matrix_minmax flags
 RANK_FROM_TOP = 1 << 63
 SETOP_KEEP_BITMAP, SETOP_OPTIMIZE = 0, 1
+COMPARE_PATH_OFFSET = 0x100  # fbk_bsi_compare: pin the general instance at base_x == base_y
 QUERY_ACCUMULATE = 1
 GROUPSEL_DEVICE, GROUPSEL_HOST = 1, 2
 GROUPSEL_NONE, GROUPSEL_COUNT, GROUPSEL_AGG = 0, 1, 2
@@ -189,6 +190,7 @@ SIGNATURES = {
     "fbk_count_matrix": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
     "fbk_bsi_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "fbk_bsi_moments": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.POINTER(Moments)]),
+    "fbk_bsi_compare": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_int64, _vp, _vp, C.c_uint32, C.c_int64, C.c_int32, _vp, _vp, C.c_uint32, C.c_uint32, _vpp, _vp]),
     "fbk_count_cube": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp]),
     "fbk_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "fbk_query_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),

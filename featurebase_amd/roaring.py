@@ -1163,6 +1163,26 @@ class Context:
         )
         return Moments(int(out.n), int(out.sum_x), int(out.sum_y), int(out.sum_xx), int(out.sum_yy), int(out.sum_xy))
 
+    def bsi_compare(self, x: Batch, base_rows_x, depth_x: int, base_x: int, y: Batch, base_rows_y, depth_y: int, base_y: int, op: int,
+                    filt: Optional[Batch] = None, rows_f=None, flags: int = 0, count_only: bool = False) -> Tuple[Optional[Batch], np.ndarray]:
+        """The Row of `value_x op value_y` per shard over exists_x ∩ exists_y ∩ filter (fbk_bsi_compare), values exact integers
+        (sign ? -magnitude : magnitude) + base: SQL WHERE x < y.  Returns (batch, counts) as bsi_range does; count_only: (None, counts)
+        with no output written on the device."""
+        bx = np.ascontiguousarray(base_rows_x, dtype=np.uint32)
+        by = np.ascontiguousarray(base_rows_y, dtype=np.uint32)
+        rf = np.ascontiguousarray(rows_f, dtype=np.uint32) if filt is not None else None
+        assert by.size == bx.size and (rf is None or rf.size == bx.size)
+        counts = np.zeros(bx.size, dtype=np.uint64)
+        h = C.c_void_p()
+        L.check(
+            self.lib.fbk_bsi_compare(
+                self.h, x.h, bx.ctypes.data, depth_x, C.c_int64(base_x), y.h, by.ctypes.data, depth_y, C.c_int64(base_y), op,
+                filt.h if filt is not None else None, rf.ctypes.data if rf is not None else None, bx.size, flags,
+                None if count_only else C.byref(h), counts.ctypes.data,
+            )
+        )
+        return (None if count_only else Batch(self, h.value)), counts
+
     def _bsi_minmax(self, fn, batch: Batch, base_rows, bit_depth: int, filt: Optional[Batch], rows_f):
         base = np.ascontiguousarray(base_rows, dtype=np.uint32)
         vals = np.zeros(base.size, dtype=np.int64)

@@ -924,6 +924,44 @@ int32_t fbk_bsi_moments(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* base_r
                         const uint32_t* base_rows_y, uint32_t depth_y, const fbk_batch* filter, const uint32_t* rows_f,
                         uint32_t n_shards, fbk_moments* out);
 
+/* ---- SQL WHERE x < y: the Row of a comparison between two int fields ------------------------------
+ * out row s = the columns of shard s with value_x op value_y, a device Row that every later operator (Count, GroupBy, Sort,
+ * Extract, Sum, TopK, the call trees of fbk_expr_*) takes as it takes any filter.  The reference has no fast path for this
+ * predicate: generatePQLCallFromBinaryExpr (sql3/planner/expressionpql.go:267-520) needs a literal on the right-hand side
+ * (planExprToValue(expr.rhs) fails on a column reference), pushdownFiltersToFilterableRelations (sql3/planner/planoptimizer.go:
+ * 393-411) then leaves the filter unpushed, and PlanOpFilter (sql3/planner/opfilter.go:107) evaluates
+ * binOpPlanExpression.Evaluate (sql3/planner/expression.go:322-) row by row on the host over an Extract of every record.  Here
+ * the answer is a function of the bit planes alone: the BSI Range scan with the constant's bit replaced by the other field's
+ * plane, every plane read once (k_bsi_compare_slot).
+ *  - The field layout is fbk_bsi_sum's (base_rows[s] + 0 exists, + 1 sign, + 2 + i plane i).  Bit depths 0..64 each; they may
+ *    differ.  x and y may be different batches, the same batch, or the same field; dense and encoded batches both work, and
+ *    containers are read in their encoded form.
+ *  - Participating columns: E_s = exists_x ∩ exists_y ∩ F.rows_f[s] (filter == NULL: no filter).  A column outside E_s is never
+ *    in the result, for FBK_BSI_NEQ too: the reference's evaluator yields NULL when either side is NULL (expression.go:348 and
+ *    the like) and the filter drops the row.
+ *  - The value of a column is (sign ? -magnitude : magnitude) + base as an EXACT integer: bit-sliced arithmetic has no width
+ *    limit, so depth 64 and bases at the int64 extremes compare correctly, with no int64 wrap-around.  This is the one place
+ *    where the value is not fbk_extract_bsi's, which wraps magnitudes >= 2^63.  A set sign over magnitude 0 is 0; sign and plane
+ *    bits outside exists are ignored.
+ *  - op is one of FBK_BSI_EQ .. FBK_BSI_GTE, evaluated as value_x op value_y.
+ *  - Output as fbk_bsi_range's: the container keys of out row s are s * 16 + slot; out_counts[s] (may be NULL) is the row's
+ *    cardinality; flags & FBK_SETOP_OPTIMIZE re-encodes and compacts the result as it does there.
+ *  - Count-only form (SELECT COUNT(*) ... WHERE x < y): out_batch == NULL with out_counts != NULL writes the counts only; no
+ *    output arena is allocated and no cell is written.  Both NULL is FBK_E_INVALID.
+ *  - FBK_COMPARE_PATH_OFFSET pins the general (two's-complement) kernel instance even when base_x == base_y, where the
+ *    sign-magnitude instance runs by default; the result is the same bit for bit.
+ *  - NULL ctx, x, y or base rows, a filter without rows_f, a depth above 64, an unknown op, unknown flags, 2^27 shards or more
+ *    and row indexes beyond a batch give FBK_E_INVALID before any launch; every error leaves the context usable.
+ *    n_shards == 0 is FBK_OK with an empty batch, as fbk_bsi_range gives.  One synchronisation per call (FBK_SETOP_OPTIMIZE adds
+ *    those of the re-encode).
+ *  - Out of this call's scope: decimal fields of different scale and timestamps of different unit.  The caller brings them to
+ *    one scale first; only the constant offset base_x - base_y is applied here. */
+#define FBK_COMPARE_PATH_OFFSET 0x100u /* pin the general (two's-complement) instance even when base_x == base_y */
+int32_t fbk_bsi_compare(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* base_rows_x, uint32_t depth_x, int64_t base_x,
+                        const fbk_batch* y, const uint32_t* base_rows_y, uint32_t depth_y, int64_t base_y, int32_t op,
+                        const fbk_batch* filter, const uint32_t* rows_f, uint32_t n_shards, uint32_t flags,
+                        fbk_batch** out_batch, uint64_t* out_counts);
+
 /* Per shard: (out_vals[s], out_counts[s]) = fragment.min / fragment.max (fragment.go:754-853):
  * the smallest / largest stored value among the columns of exists ∩ filter and the number of
  * columns holding it; (0, 0) when there is no such column.  Sign-magnitude planes, MSB -> LSB

@@ -146,8 +146,9 @@ struct SignedRows {
 
 // A PQL bitmap call (the subset on the hot path).
 struct Call {
-  enum Kind { kRow, kRange, kBetween, kIntersect, kUnion, kDifference, kXor, kNot, kAll, kShift, kPrecomputed } kind = kRow;
+  enum Kind { kRow, kRange, kBetween, kIntersect, kUnion, kDifference, kXor, kNot, kAll, kShift, kPrecomputed, kCompare } kind = kRow;
   std::string field;
+  std::string field2;  // Compare: the right-hand int field
   uint64_t row = 0;    // Row(field=row)
   int32_t op = 0;      // FBK_BSI_* for Row(field <op> value)
   int64_t value = 0, value2 = 0;
@@ -166,6 +167,16 @@ struct Call {
     c.field = std::move(f);
     c.op = op;
     c.value = v;
+    return c;
+  }
+  // Row(field_x <op> field_y): the columns where both int fields have a value and value_x op value_y — SQL WHERE x < y, which the
+  // reference's planner leaves to a row-by-row filter on the host (sql3/planner/opfilter.go:107).  One fbk_bsi_compare.
+  static Call Compare(std::string fx, int32_t op, std::string fy) {
+    Call c;
+    c.kind = kCompare;
+    c.field = std::move(fx);
+    c.op = op;
+    c.field2 = std::move(fy);
     return c;
   }
   static Call Between(std::string f, int64_t lo, int64_t hi) {
@@ -471,6 +482,11 @@ class Executor {
       ++library_calls;
       check(fbk_expr_count(idx_.ctx_, b.leaves.data(), uint32_t(b.leaves.size()), b.prog.data(), uint32_t(b.prog.size()), uint32_t(counts.size()), counts.data()));
       for (uint64_t x : counts) n += x;
+      return n;
+    }
+    if (c.kind == Call::kCompare && !shards().empty()) {  // SELECT COUNT(*) ... WHERE x < y: the count-only form
+      uint64_t n = 0;
+      (void)compare(c, &n);
       return n;
     }
     RowSet r = eval(c);
@@ -1243,6 +1259,21 @@ class Executor {
     return fresh(o);
   }
 
+  // Row(field_x <op> field_y): one fbk_bsi_compare with the two fields' Bases.  count: the count-only form, nothing is materialised.
+  RowSet compare(const Call& c, uint64_t* count = nullptr) {
+    const Index::IntField &fx = idx_.ints_.at(c.field), &fy = idx_.ints_.at(c.field2);
+    const std::vector<uint32_t> bx = base_rows(fx), by = base_rows(fy);
+    std::vector<uint64_t> counts(count ? bx.size() : 0);
+    fbk_batch* o = nullptr;
+    ++library_calls;
+    check(fbk_bsi_compare(idx_.ctx_, fx.batch, bx.data(), fx.bit_depth, fx.base, fy.batch, by.data(), fy.bit_depth, fy.base, c.op, nullptr, nullptr, uint32_t(bx.size()),
+                          FBK_SETOP_OPTIMIZE, count ? nullptr : &o, count ? counts.data() : nullptr));
+    if (!count) return fresh(o);
+    *count = 0;
+    for (uint64_t x : counts) *count += x;
+    return RowSet();
+  }
+
   // ---- a call tree as ONE fbk_expr_* call -----------------------------------------------------------------------------------
   static bool is_operator(Call::Kind k) { return k == Call::kIntersect || k == Call::kUnion || k == Call::kDifference || k == Call::kXor || k == Call::kNot; }
   struct ExprBuild {
@@ -1307,7 +1338,8 @@ class Executor {
         else b.push(f.batch, base_rows(f), r.what == RangeSpec::kScan ? FBK_EXPR_BSI : FBK_EXPR_BETWEEN, r.op, f.bit_depth, r.lo, r.hi);
         return 1;
       }
-      case Call::kShift:  // crosses containers: a call of its own, its result a ROW leaf
+      case Call::kShift:    // crosses containers: a call of its own, its result a ROW leaf
+      case Call::kCompare:  // two fields' planes: a call of its own (fbk_bsi_compare), its result a ROW leaf
         b.push(eval_nodes(c));
         return 1;
       default: break;
@@ -1411,6 +1443,7 @@ class Executor {
       case Call::kRow: return leaf_row(c.field, c.row);
       case Call::kRange:
       case Call::kBetween: return range(c);
+      case Call::kCompare: return compare(c);
       case Call::kAll: return leaf_row(Index::kExistence, 0);
       case Call::kPrecomputed: {
         if (!c.pre || !c.pre->batch) throw Error(FBK_E_INVALID, "Precomputed() without a result");

@@ -1,0 +1,35 @@
+"""Call::Compare (include/fbk_executor.hpp, one fbk_bsi_compare) against a brute force over a small index with two int fields of
+different Base, all six operators, both fuse_calls settings: tests/cpp/test_compare.cpp, built the way tests/test_cpp_moments.py
+builds its program; the compile check runs everywhere, the run needs the GPU."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "test_compare.cpp")
+BIN = os.path.join(ROOT, "build", "test_compare")
+
+
+def compile_it():
+    import __graft_entry__ as g
+
+    g.build()
+    os.makedirs(os.path.dirname(BIN), exist_ok=True)
+    lib = os.path.join(ROOT, "featurebase_amd", "csrc")
+    subprocess.check_call(
+        ["g++", "-std=c++17", "-O2", "-Wall", "-pthread", "-I", os.path.join(ROOT, "include"), SRC, "-L", lib, "-lfbk", f"-Wl,-rpath,{lib}", "-Wl,-rpath-link,/opt/rocm/lib", "-o", BIN]
+    )
+
+
+def test_compare_compiles():
+    compile_it()
+    assert os.path.exists(BIN)
+
+
+@pytest.mark.gpu
+def test_compare_on_gpu():
+    compile_it()
+    out = subprocess.run([BIN], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "compare ok" in out.stdout
