@@ -1394,7 +1394,9 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_output.inc"
 #include "fbk_plan_api.inc"
 #include "fbk_dense_operands.inc"
-#include "fbk_query_api.inc"         // folds, Rows / Flip / Shift / compaction, the BSI aggregates
+#include "fbk_query_api.inc"         // shared helpers (check_rows, FilterArgs, RowRecords), Rows / Flip / Shift / compaction
+#include "fbk_fold_api.inc"          // the n-way folds: FoldPlan
+#include "fbk_bsi_api.inc"           // the BSI calls: BsiRangePlan, BsiSumPlan
 #include "fbk_count_matrix_api.inc"  // the GroupBy count matrix: MatrixPlan; its rules: fbk_count_matrix_plan.h
 #include "fbk_matrix_sum_api.inc"
 #include "fbk_moments_api.inc"

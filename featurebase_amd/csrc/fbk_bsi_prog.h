@@ -1,5 +1,5 @@
 // fbk_bsi_prog.h — the plane programs of the BSI range predicates, HIP-free (included by the kernels for the opcodes, by
-// fbk_query_api.inc for the one-shot and prepared Range calls, by fbk_expr_plan.h for the BSI leaves of a call tree, and by
+// fbk_bsi_api.inc for the one-shot and prepared Range calls, by fbk_expr_plan.h for the BSI leaves of a call tree, and by
 // the stand-alone planner check of the tests).
 #pragma once
 

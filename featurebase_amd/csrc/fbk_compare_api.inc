@@ -65,8 +65,7 @@ int32_t fbk_bsi_compare(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* base_r
     HIP_TRY(dcnt.alloc(ctx, uint64_t(n_shards) * 8));
     HIP_TRY(hipMemsetAsync(dcnt.p, 0, uint64_t(n_shards) * 8, ctx->stream));
   }
-  // optimize() asked for: applied by the kernel itself (option setop_direct_encode = 2; otherwise the separate re-encode pass)
-  const bool enc = out_batch && (flags & FBK_SETOP_OPTIMIZE) && ctx->opt.setop_direct_encode == 2;
+  const bool enc = out_batch && out.kernel_encodes(flags & uint32_t(FBK_SETOP_OPTIMIZE));
   const FilterArgs f(filter, dr[2]);
   fbk::CompareArgs a{};
   a.xslots = x->d_slots, a.xarena = x->d_arena, a.xbase = dr[0];
@@ -91,8 +90,7 @@ int32_t fbk_bsi_compare(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* base_r
     HIP_TRY(back.finish());  // the call's one synchronisation
     return FBK_OK;
   }
-  const uint32_t oflags = flags & uint32_t(FBK_SETOP_OPTIMIZE);
-  if (int32_t rc = out.finish(enc ? 0u : oflags, n_shards, out_counts, enc)) return rc;  // (synchronises)
+  if (int32_t rc = out.finish(n_shards, out_counts)) return rc;  // (synchronises)
   *out_batch = out.release();
   return FBK_OK;
 } FBK_ABI_CATCH(ctx)

@@ -13,6 +13,7 @@ struct ExprProgram {
   DevBuf buf;
   uint64_t off_leaves = 0, off_prog = 0;
   uint32_t n_shards = 0;
+  bool encode = false;  // a prepared query with rows: FBK_SETOP_OPTIMIZE, the kernel encodes
   const fbk::ExprLeaf* d_leaves() const { return reinterpret_cast<const fbk::ExprLeaf*>(static_cast<const uint8_t*>(buf.p) + off_leaves); }
   const uint32_t* d_prog() const { return reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(buf.p) + off_prog); }
   uint32_t lds_bytes() const { return (1u + plan.slots) * 8192u; }
@@ -22,6 +23,13 @@ struct ExprProgram {
   uint32_t agg = 0, agg_depth = 0;
   // words per shard the aggregate leaves on the device: {psum, nsum, count}, or 16 slots of {magnitude, count | scan flag}
   uint64_t agg_words() const { return agg == FBK_AGG_SUM ? 3 : 2 * uint64_t(fbk::kSlots); }
+};
+
+// Declared after the ExprProgram (fbk_expr_topk_api.inc: the ExprRows) of a one-shot call: the upload reads P.blob, nothing of it may go
+// while the stream still holds work.
+struct StreamDrain {
+  fbk_ctx* c;
+  ~StreamDrain() { (void)hipStreamSynchronize(c->stream); }
 };
 
 int32_t expr_args_ok(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog) {
@@ -95,6 +103,14 @@ int32_t expr_launch(fbk_ctx* ctx, ExprProgram& P, uint8_t* arenaO, Slot* outSlot
   return FBK_OK;
 }
 
+// a run of the prepared form: memset (unless the counts accumulate) + ONE launch; o == NULL: FBK_EXPR_COUNT_ONLY
+int32_t expr_enqueue(fbk_ctx* ctx, ExprProgram& P, fbk_batch* o, u64* d_counts, bool accumulate) {
+  if (!accumulate) HIP_TRY(hipMemsetAsync(d_counts, 0, uint64_t(P.n_shards) * 8, ctx->stream));
+  if (int32_t rc = expr_launch(ctx, P, o ? o->d_arena : nullptr, o ? o->d_slots : nullptr, nullptr, d_counts, o && P.encode)) return rc;
+  if (o) slots_rewritten(o);
+  return FBK_OK;
+}
+
 // output keys of a tree whose first pushed leaf is a ROW: those of that row (a row without containers: 0), as a fold takes its
 // first row's.  A tree that starts with a BSI predicate keeps the default keys (row ordinal * 16 + slot), as fbk_bsi_range does.
 int32_t expr_output_keys(const fbk_expr_leaf* leaves, const ExprProgram& P, fbk_batch* o) {
@@ -148,20 +164,28 @@ int32_t expr_agg_launch(fbk_ctx* ctx, ExprProgram& P, u64* d_out) {
   return FBK_OK;
 }
 
+// a run of the prepared form into d_out; Sum: zeroed first unless it accumulates
+int32_t expr_agg_enqueue(fbk_ctx* ctx, ExprProgram& P, u64* d_out, bool accumulate) {
+  if (P.agg == FBK_AGG_SUM && !accumulate) HIP_TRY(hipMemsetAsync(d_out, 0, uint64_t(P.n_shards) * P.agg_words() * 8, ctx->stream));
+  return expr_agg_launch(ctx, P, d_out);
+}
+
 // the downloaded words -> per-shard (value, count), as fbk_bsi_sum / fbk_bsi_min / fbk_bsi_max give them; either output may be NULL
 void expr_agg_fold(const ExprProgram& P, const u64* h, int64_t* out_vals, uint64_t* out_counts) {
   std::vector<int64_t> v(P.n_shards);
   std::vector<uint64_t> c(P.n_shards);
-  if (P.agg == FBK_AGG_SUM) {
-    for (uint32_t s = 0; s < P.n_shards; ++s) {  // Total(): int64(psum) - int64(nsum) (roaring/filter.go:1106-1108)
-      v[s] = int64_t(h[s * 3 + 0] - h[s * 3 + 1]);
-      c[s] = h[s * 3 + 2];
-    }
-  } else {
-    bsi_minmax_fold(h, P.n_shards, P.agg == FBK_AGG_MAX ? 1u : 0u, v.data(), c.data());
-  }
+  if (P.agg == FBK_AGG_SUM) bsi_sum_fold(h, P.n_shards, v.data(), c.data());
+  else bsi_minmax_fold(h, P.n_shards, P.agg == FBK_AGG_MAX ? 1u : 0u, v.data(), c.data());
   if (out_vals) std::memcpy(out_vals, v.data(), uint64_t(P.n_shards) * 8);
   if (out_counts) std::memcpy(out_counts, c.data(), uint64_t(P.n_shards) * 8);
+}
+
+// the raw words of a run at d_raw -> per-shard (value, count) on the host (one synchronisation)
+int32_t expr_agg_read(fbk_ctx* ctx, const ExprProgram& P, const void* d_raw, int64_t* out_vals, uint64_t* out_counts) {
+  std::vector<u64> h;
+  if (int32_t rc = download_words(ctx, d_raw, uint64_t(P.n_shards) * P.agg_words(), h)) return rc;
+  expr_agg_fold(P, h.data(), out_vals, out_counts);
+  return FBK_OK;
 }
 
 }  // namespace
@@ -178,15 +202,11 @@ int32_t fbk_expr_count(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_lea
   if (int32_t rc = set_device(ctx)) return rc;
   ExprProgram P;
   DevBuf dcnt;
-  struct Drain {  // the upload reads P.blob: nothing of P may go while the stream still holds work
-    fbk_ctx* c;
-    ~Drain() { (void)hipStreamSynchronize(c->stream); }
-  } drain{ctx};
+  StreamDrain drain{ctx};
   if (int32_t rc = expr_prepare(ctx, leaves, n_leaves, prog, n_prog, n_shards, P)) return rc;
   if (n_shards == 0) return FBK_OK;
   HIP_TRY(dcnt.alloc(ctx, uint64_t(n_shards) * 8));
-  HIP_TRY(hipMemsetAsync(dcnt.p, 0, uint64_t(n_shards) * 8, ctx->stream));
-  if (int32_t rc = expr_launch(ctx, P, nullptr, nullptr, nullptr, dcnt.as<u64>(), false)) return rc;
+  if (int32_t rc = expr_enqueue(ctx, P, nullptr, dcnt.as<u64>(), false)) return rc;
   D2H back(ctx);
   HIP_TRY(back.add(out_counts, dcnt.p, uint64_t(n_shards) * 8));
   HIP_TRY(back.finish());
@@ -204,19 +224,14 @@ int32_t fbk_expr_eval(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leav
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
   ExprProgram P;
-  struct Drain {
-    fbk_ctx* c;
-    ~Drain() { (void)hipStreamSynchronize(c->stream); }
-  } drain{ctx};
+  StreamDrain drain{ctx};
   CellOutput out;  // (after the drain guard: freed first, and its own destructor drains as well)
   if (int32_t rc = expr_prepare(ctx, leaves, n_leaves, prog, n_prog, n_shards, P)) return rc;
   if (int32_t rc = out.alloc(ctx, n_shards, n_shards, "expr")) return rc;
   if (n_shards) {
     if (int32_t rc = expr_output_keys(leaves, P, out.batch())) return rc;
-    // optimize() asked for: applied by the kernel itself (option setop_direct_encode = 2; otherwise the separate re-encode pass)
-    const bool enc = (flags & FBK_SETOP_OPTIMIZE) && ctx->opt.setop_direct_encode == 2;
-    if (int32_t rc = expr_launch(ctx, P, out.batch()->d_arena, out.batch()->d_slots, out.runs(), out.counts(), enc)) return rc;
-    if (int32_t rc = out.finish(enc ? (flags & ~uint32_t(FBK_SETOP_OPTIMIZE)) : flags, n_shards, out_counts, enc)) return rc;
+    if (int32_t rc = expr_launch(ctx, P, out.batch()->d_arena, out.batch()->d_slots, out.runs(), out.counts(), out.kernel_encodes(flags))) return rc;
+    if (int32_t rc = out.finish(n_shards, out_counts)) return rc;
   }
   (void)hipStreamSynchronize(ctx->stream);
   *out_batch = out.release();
@@ -234,20 +249,12 @@ int32_t fbk_expr_bsi_agg(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_l
   if (int32_t rc = set_device(ctx)) return rc;
   ExprProgram P;
   DevBuf dout;
-  struct Drain {  // the upload reads P.blob: nothing of P may go while the stream still holds work
-    fbk_ctx* c;
-    ~Drain() { (void)hipStreamSynchronize(c->stream); }
-  } drain{ctx};
+  StreamDrain drain{ctx};
   if (int32_t rc = expr_agg_prepare(ctx, leaves, n_leaves, prog, n_prog, n_shards, agg, batch, base_rows, bit_depth, P)) return rc;
   if (n_shards == 0) return FBK_OK;
-  const uint64_t n_words = uint64_t(n_shards) * P.agg_words();
-  HIP_TRY(dout.alloc(ctx, n_words * 8));
-  if (agg == FBK_AGG_SUM) HIP_TRY(hipMemsetAsync(dout.p, 0, n_words * 8, ctx->stream));
-  if (int32_t rc = expr_agg_launch(ctx, P, dout.as<u64>())) return rc;
-  std::vector<u64> h;
-  if (int32_t rc = download_words(ctx, dout, n_words, h)) return rc;
-  expr_agg_fold(P, h.data(), out_vals, out_counts);
-  return FBK_OK;
+  HIP_TRY(dout.alloc(ctx, uint64_t(n_shards) * P.agg_words() * 8));
+  if (int32_t rc = expr_agg_enqueue(ctx, P, dout.as<u64>(), false)) return rc;
+  return expr_agg_read(ctx, P, dout.p, out_vals, out_counts);
 } FBK_ABI_CATCH(ctx)
 
 }  // extern "C"

@@ -19,10 +19,6 @@ struct ExprRows {
   DevBuf drows;
   TopnBuffers B;
 };
-struct StreamDrain {  // declared after an ExprRows: the upload reads P.blob, nothing of R may go while the stream still holds work
-  fbk_ctx* c;
-  ~StreamDrain() { (void)hipStreamSynchronize(c->stream); }
-};
 
 int32_t expr_rows_args_ok(fbk_ctx* ctx, const fbk_expr_leaf* leaves, uint32_t n_leaves, const uint32_t* prog, uint32_t n_prog, const fbk_batch* a,
                           const uint32_t* rows_a, uint32_t n_a, uint32_t n_shards) {

@@ -164,6 +164,14 @@ struct CellOutput {
   int32_t finish(uint32_t flags, uint64_t n_counts, uint64_t* out_counts, bool encoded_in_cells = false) {
     return finish_output(ctx, o, flags, runs(), counts(), n_counts, out_counts, encoded_in_cells);
   }
+  // optimize() asked for: does the kernel apply it itself (option setop_direct_encode = 2; otherwise the separate re-encode
+  // pass)?  The answer is the kernel's encode argument, and finish(n_counts, out_counts) goes by it.
+  bool kernel_encodes(uint32_t flags) {
+    enc = (flags & FBK_SETOP_OPTIMIZE) && ctx->opt.setop_direct_encode == 2;
+    fin_flags = enc ? flags & ~uint32_t(FBK_SETOP_OPTIMIZE) : flags;
+    return enc;
+  }
+  int32_t finish(uint64_t n_counts, uint64_t* out_counts) { return finish(fin_flags, n_counts, out_counts, enc); }
   fbk_batch* release() {
     fbk_batch* b = o;
     o = nullptr;
@@ -173,6 +181,8 @@ struct CellOutput {
  private:
   fbk_ctx* ctx = nullptr;
   fbk_batch* o = nullptr;
+  uint32_t fin_flags = 0;
+  bool enc = false;
   DevBuf druns, dcnt;  // (freed after the destructor's drain)
 };
 

@@ -1,5 +1,5 @@
 // fbk_topn_api.inc — host side of the TopK / TopN family (included by fbk.hip after fbk_expr_api.inc: a call tree may be the filter): fbk_topk,
-// fbk_topn, fbk_topn_partials, fbk_topk_bsi here; fbk_query_topn (fbk_prepared_api.inc), fbk_group_topn (fbk_group_api.inc) and fbk_expr_row_counts /
+// fbk_topn, fbk_topn_partials, fbk_topk_bsi and the TopnPlan of fbk_query_topn here; fbk_group_topn (fbk_group_api.inc) and fbk_expr_row_counts /
 // _topk / _topn (fbk_expr_topk_api.inc) are built from the same pieces: topn_args_ok (the limits), TopnSource (the filter), TopnBuffers (the device
 // vectors, sized by fbk_topn_plan.h), topn_totals_enqueue (the passes: ONE body), TopnSort / topn_radix_enqueue / topn_order_locked (the ordering).
 #include "fbk_topn_plan.h"
@@ -173,6 +173,74 @@ int32_t topn_radix_enqueue(fbk_ctx* ctx, TopnSort& s, u64* d_total, uint32_t n_a
   HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(s.dtmp.p, tb, d_total, s.dsk.as<u64>(), s.dval.as<uint32_t>(), s.dsv.as<uint32_t>(), int(n_a), 0, 64, ctx->stream));
   hipLaunchKernelGGL(fbk::k_count_nonzero_desc, dim3(1), dim3(1), 0, ctx->stream, s.dsk.as<u64>(), n_a, s.dnz.as<uint32_t>());
   HIP_TRY(hipGetLastError());
+  return FBK_OK;
+}
+
+// The ordering of a prepared TopN's run, launch only.  A field of a few thousand rows: every row finds its own rank (one launch; the radix sort's
+// five launches were 30 of the 154 us of TopN(10) over config 3's 64 rows); larger fields: the radix sort.
+int32_t topn_order_enqueue(fbk_ctx* ctx, TopnSort& s, u64* d_total, uint32_t n_a) {
+  if (n_a > fbk::kRankSortMax) return topn_radix_enqueue(ctx, s, d_total, n_a);
+  HIP_TRY(hipMemsetAsync(s.dnz.p, 0, 4, ctx->stream));
+  hipLaunchKernelGGL(fbk::k_rank_sort_desc, dim3((n_a + 255) / 256), dim3(256), 0, ctx->stream, d_total, n_a, s.dsk.as<u64>(), s.dsv.as<uint32_t>(), s.dnz.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  return FBK_OK;
+}
+
+// fbk_query_topn (fragment.top's per-shard rules, executeTopN's sum over shards: fbk_topn) with nothing left to the host: row lists resident, the
+// n asked for, the pass buffers with their plan (thresholds, the candidate pass's n under the semantics in force at prepare), the resolved records
+// of the field's rows, and the scratch of the on-device ordering — all sized at prepare.  A run leaves {counts, indexes, number of non-empty rows}
+// on the device; topn_read copies the first n.
+struct TopnPlan {
+  const fbk_batch *a = nullptr, *filter = nullptr;
+  uint32_t n_a = 0, n_shards = 0, top_n = 0;
+  DevBuf rows;
+  const uint32_t* dr[2] = {nullptr, nullptr};  // field rows and filter rows on the device
+  TopnBuffers buf;
+  TopnSort sort;
+  RowRecords recs;
+};
+
+// validates and uploads the row lists, sizes the buffers; d_total [n_a]: the totals of every run (the query's result)
+int32_t topn_prepare(fbk_ctx* ctx, TopnPlan& P, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* filter, const uint32_t* rows_f, uint32_t n_shards,
+                     uint32_t n, uint64_t min_threshold, uint64_t tanimoto_threshold, u64* d_total) {
+  P.a = a;
+  P.filter = filter;
+  P.n_a = n_a;
+  P.n_shards = n_shards;
+  P.top_n = n;
+  if (int32_t rc = check_rows(rows_a, uint64_t(n_shards) * n_a, a->n_rows, "topk rows")) return rc;
+  // (the semantics and option matrix_pass_kb in force when the query is prepared)
+  const fbk_topn_plan::Sizes sizes = topn_plan(ctx, n_a, n_shards, TopnSource{filter}, min_threshold, tanimoto_threshold, topn_cand_n(ctx, n, n_a, true));
+  if (int32_t rc = upload_rows_multi(ctx, {{rows_a, uint64_t(n_shards) * n_a, UINT32_MAX}, {rows_f, filter ? uint64_t(n_shards) : 0, filter ? filter->n_rows : UINT32_MAX}}, P.rows, P.dr))
+    return rc;
+  hipError_t e = P.buf.alloc(ctx, sizes, d_total);
+  if (e == hipSuccess) e = P.sort.alloc(ctx, n_a);
+  if (e != hipSuccess) return fail(FBK_E_NOMEM, std::string("query: ") + hipGetErrorString(e));
+  return FBK_OK;
+}
+
+int32_t topn_enqueue(fbk_ctx* ctx, TopnPlan& P) {
+  const Slot* recs = nullptr;
+  if (P.filter)  // (the counts against the filter read them; without a filter the stored cardinalities answer)
+    if (int32_t rc = query_row_records(ctx, P.recs, P.a, P.dr[0], P.n_shards, P.n_a, &recs)) return rc;
+  if (int32_t rc = topn_totals_enqueue(ctx, P.a, P.dr[0], TopnSource{P.filter, P.dr[1], recs}, P.buf, /*mask=*/true)) return rc;
+  return topn_order_enqueue(ctx, P.sort, P.buf.d_total, P.n_a);
+}
+
+// out_index = uint32 {number of results, then that many row indexes} (1 + min(n, n_a) words, n = 0: 1 + n_a); out_count = uint64 counts of those rows
+int32_t topn_read(fbk_ctx* ctx, const TopnPlan& P, uint32_t* out_index, uint64_t* out_count) {
+  uint32_t nz = 0;
+  D2H back(ctx);
+  HIP_TRY(back.add(&nz, P.sort.dnz.p, 4));
+  HIP_TRY(back.finish());
+  const uint32_t want = P.top_n ? std::min(P.top_n, nz) : nz;  // rows without a single common column are not results
+  if (out_index) out_index[0] = want;
+  if (want) {
+    D2H back2(ctx);
+    if (out_index) HIP_TRY(back2.add(out_index + 1, P.sort.dsv.p, uint64_t(want) * 4));
+    if (out_count) HIP_TRY(back2.add(out_count, P.sort.dsk.p, uint64_t(want) * 8));
+    HIP_TRY(back2.finish());
+  }
   return FBK_OK;
 }
 

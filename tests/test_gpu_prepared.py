@@ -496,3 +496,91 @@ def test_a_kept_count_matrix_plan_across_its_modes(gpu_ctx):
             gpu_ctx.set_option(o, v)
         M.free()
         Dn.free()
+
+
+def _run_mode_batch():
+    """2 shards x 13 rows: three rows of field A, three of field B, one filter row, and an int field of depth 4 (exists, sign,
+    four planes).  Every row has an array, a run and a bitmap container (slots 0 .. 2); the field has negative values."""
+    rng = D.rng_for(8500)
+    makers = (lambda: np.unique(rng.integers(0, 65536, 1500)).astype(np.int64), lambda: D.vals_runs(rng, 16, 0.5), lambda: D.vals_density(rng, 0.4))
+    rows = []
+    for s in range(2):
+        for r in range(8):  # A, B, the filter, exists
+            rows.append({(len(rows) * 16 + sl): makers[(r + sl) % 3]() for sl in range(3)})
+        exists = rows[-1]
+        for p in (0.3, 0.5, 0.5, 0.5, 0.5):  # sign and planes: subsets of exists
+            rows.append({(len(rows) * 16 + (k & 15)): v[rng.random(v.size) < p] for k, v in exists.items()})
+    assert all(np.intersect1d(rows[s * 13 + 8][(s * 13 + 8) * 16], rows[s * 13 + 9][(s * 13 + 9) * 16]).size for s in range(2))  # negative values
+    conts = [{k: D.fbk_container_of_vals(v) for k, v in row.items()} for row in rows]
+    assert {c.typ for row in conts[:16] for c in row.values()} == {L.TYPE_ARRAY, L.TYPE_RUN, L.TYPE_BITMAP}
+    g = np.arange(26).reshape(2, 13)
+    return conts, g[:, 0:3], g[:, 3:6], g[:, 6], g[:, 7]
+
+
+def test_run_modes_by_kind(gpu_ctx):
+    """Which kinds of prepared query take FBK_QUERY_ACCUMULATE and which a caller's device buffer (the rules of fbk_query_run): every
+    kind accepts or refuses each of the two with FBK_E_INVALID; a refused run leaves the result of the run before it readable and
+    unchanged; an accepted accumulate doubles the result, an accepted redirect reads back what the query's own buffer held."""
+    import torch
+    from featurebase_amd.roaring import bsi_leaf, compile_expr, row_leaf
+
+    conts, ra, rb, rf, base = _run_mode_batch()
+    M = gpu_ctx.upload(conts)
+    depth = 4
+    leaves, prog = compile_expr(("and", row_leaf(M, ra[:, 0]), ("or", row_leaf(M, rb[:, 1]), bsi_leaf(M, base, L.BSI_LT, depth, 2))))
+    # kind -> (prepare, accumulate accepted, a caller's buffer accepted)
+    table = {
+        "count matrix": (lambda: gpu_ctx.prepare_count_matrix(M, ra, M, rb, M, rf), True, True),
+        "GroupBy Sum": (lambda: gpu_ctx.query_count_matrix_sum(M, ra, M, rb, M, base, depth, M, rf), False, False),
+        "fold count": (lambda: gpu_ctx.prepare_fold_intersection_count(L.OP_OR, M, ra, M, rf), True, True),
+        "fold rows": (lambda: gpu_ctx.prepare_fold(L.OP_OR, M, ra), False, True),
+        "BSI Sum": (lambda: gpu_ctx.prepare_bsi_sum(M, base, depth, filt=M, rows_f=rf), False, True),
+        "Sum(Range)": (lambda: gpu_ctx.prepare_bsi_sum(M, base, depth, L.BSI_GT, 3, M, rf), False, True),
+        "BSI Range rows": (lambda: gpu_ctx.prepare_bsi_range(M, base, L.BSI_LT, depth, 5), False, True),
+        "expr rows": (lambda: gpu_ctx.query_expr(leaves, prog), False, False),
+        "expr count-only": (lambda: gpu_ctx.query_expr(leaves, prog, count_only=True), True, True),
+        "expr Sum": (lambda: gpu_ctx.query_expr_bsi(L.AGG_SUM, leaves, prog, M, base, depth), True, True),
+        "expr Min": (lambda: gpu_ctx.query_expr_bsi(L.AGG_MIN, leaves, prog, M, base, depth), False, False),
+        "TopN": (lambda: gpu_ctx.prepare_topn(M, ra, 2, M, rf), False, False),
+    }
+    with_rows = ("fold rows", "BSI Range rows", "expr rows")
+
+    def state(q, kind):
+        r = q.read()
+        parts = [np.asarray(x) for x in (r if isinstance(r, tuple) else (r,))]
+        if kind in with_rows:
+            parts.append(_words_of(q.output()))
+        return parts
+
+    def same(a, b):
+        return len(a) == len(b) and all(x.shape == y.shape and (x == y).all() for x, y in zip(a, b))
+
+    try:
+        for kind, (prepare, acc_ok, dev_ok) in table.items():
+            q = prepare()
+            q.run()
+            first = state(q, kind)
+            assert any(p.any() for p in first), kind
+            cell = torch.zeros(q.result_ptr()[1] // 8, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
+            for mode, ok, args in (("accumulate", acc_ok, dict(accumulate=True)), ("device_out", dev_ok, dict(device_ptr=cell.data_ptr()))):
+                if ok:
+                    q.run(**args)
+                    got = state(q, kind)
+                    exp = [2 * p for p in first] if mode == "accumulate" else first
+                    assert same(got, exp), (kind, mode)
+                    q.run()  # (back to the query's own buffer, overwritten)
+                    assert same(state(q, kind), first), (kind, mode)
+                else:
+                    with pytest.raises(L.FbkError) as e:
+                        q.run(**args)
+                    assert e.value.code == L.FBK_E_INVALID, (kind, mode)
+                    assert same(state(q, kind), first), (kind, mode)
+            if not acc_ok and not dev_ok:
+                with pytest.raises(L.FbkError) as e:
+                    q.run(cell.data_ptr(), accumulate=True)
+                assert e.value.code == L.FBK_E_INVALID, kind
+                assert same(state(q, kind), first), kind
+            q.free()
+    finally:
+        M.free()
