@@ -38,6 +38,7 @@
 #include "fbk_extract.hip.h"
 #include "fbk_sort.hip.h"
 #include "fbk_quantile.hip.h"
+#include "fbk_group_quantile.hip.h"
 #include "fbk_distinct_rows.hip.h"
 #include "fbk_expr.hip.h"
 #include "fbk_expr_topk.hip.h"
@@ -1408,6 +1409,7 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_extract_api.inc"
 #include "fbk_sort_api.inc"
 #include "fbk_quantile_api.inc"
+#include "fbk_group_quantile_api.inc"
 #include "fbk_distinct_rows_api.inc"
 #include "fbk_expr_api.inc"
 #include "fbk_topn_api.inc"

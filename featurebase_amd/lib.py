@@ -19,6 +19,7 @@ TYPE_NIL, TYPE_ARRAY, TYPE_BITMAP, TYPE_RUN = 0, 1, 2, 3
 OP_AND, OP_OR, OP_XOR, OP_ANDNOT = 0, 1, 2, 3
 SORT_DESC, SORT_KEEP_ZERO = 1, 2
 MINMAX_AUTO, MINMAX_DESCENT, MINMAX_SCATTER = 0, 1, 2  # fbk_count_matrix_minmax flags
+GQUANT_AUTO, GQUANT_LDS, GQUANT_GLOBAL = 0, 1, 2  # fbk_count_matrix_quantiles flags
 RANK_FROM_TOP = 1 << 63
 SETOP_KEEP_BITMAP, SETOP_OPTIMIZE = 0, 1
 COMPARE_PATH_OFFSET = 0x100  # fbk_bsi_compare: pin the general instance at base_x == base_y
@@ -196,6 +197,8 @@ SIGNATURES = {
     "fbk_query_count_matrix_sum": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vpp]),
     "fbk_count_matrix_distinct": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
     "fbk_count_matrix_minmax": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "fbk_count_matrix_quantiles": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32,
+                                               _vp, _vp, _vp]),
     "fbk_count_matrix_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),
     "fbk_count_cube_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),
     "fbk_count_matrix_sum_select": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _u64p, _u64p]),

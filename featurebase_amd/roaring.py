@@ -1018,6 +1018,25 @@ class Context:
         del keep
         return mins, maxs, cmin, cmax
 
+    def count_matrix_quantiles(self, a: Batch, rows_a, b: Optional[Batch], rows_b, bsi: Batch, base_rows, bit_depth: int, fractions,
+                               filt: Optional[Batch] = None, rows_f=None, path: int = 0):
+        """GroupBy with a percentile of an int field per group (SQL PERCENTILE_DISC(x, num / den) ... GROUP BY a, b): for every pair
+        (i, j) and every (num, den) of `fractions` the value s[max(1, ceil(N * num / den)) - 1] of the ascending stored values over
+        A_i ∩ B_j ∩ filt ∩ exists, taken over all the shards together, and how many columns hold exactly it (b = None: the
+        one-field form, one column).  Arguments as count_matrix_sum; at most 16 fractions, den <= 2^20; path: L.GQUANT_AUTO, _LDS
+        (few groups) or _GLOBAL.  Returns (values int64 [n_a, n_b, n_q], counts uint64 [n_a, n_b, n_q], totals uint64 [n_a, n_b]);
+        an empty group is (0, 0) with total 0; the caller adds Base.  No fractions: the totals alone."""
+        args, keep, n_shards, n_a, n_b = self._msum_args(a, rows_a, b, rows_b, bsi, base_rows, filt, rows_f)
+        fr = np.ascontiguousarray(fractions, dtype=np.uint32).reshape(-1, 2)
+        n_q = fr.shape[0]
+        num, den = np.ascontiguousarray(fr[:, 0]), np.ascontiguousarray(fr[:, 1])
+        vals, cnts = np.zeros((n_a, n_b, n_q), dtype=np.int64), np.zeros((n_a, n_b, n_q), dtype=np.uint64)
+        totals = np.zeros((n_a, n_b), dtype=np.uint64)
+        L.check(self.lib.fbk_count_matrix_quantiles(*args, bit_depth, n_shards, num.ctypes.data if n_q else None, den.ctypes.data if n_q else None, n_q, path,
+                                                    vals.ctypes.data if n_q else None, cnts.ctypes.data if n_q else None, totals.ctypes.data))
+        del keep
+        return vals, cnts, totals
+
     # -- GroupBy having / sort / offset / limit ---------------------------------------------------
     def _select(self, call, args, sel, has_agg: bool, cap: Optional[int], aggs_slot: bool = True):
         """`call`(*args, sel, out_cells, out_counts[, out_aggs], cap, out_n, out_matched), one retry with the reported size when

@@ -640,6 +640,55 @@ int32_t fbk_count_matrix_minmax(fbk_ctx* ctx, const fbk_batch* a, const uint32_t
                                 uint32_t flags, int64_t* out_min, int64_t* out_max, uint64_t* out_min_counts,
                                 uint64_t* out_max_counts);
 
+/* ---- GroupBy with a percentile of an int field per group (SQL PERCENTILE_DISC(x, p) ... GROUP BY a, b) -----
+ * For every group g = i*n_b + j, over ALL the shards given together (X_s = A.rows_a[s*n_a+i] ∩ B.rows_b[s*n_b+j] ∩ F.rows_f[s] ∩
+ * exists, X = the union of the X_s), with s_g[0 .. N_g) the values of the columns of X in ascending order:
+ *   out_totals[g]           N_g, the number of columns of X; always written
+ *   out_values[g*n_q + q]   s_g[k], k = max(1, ceil(N_g * q_num[q] / q_den[q])) - 1 in exact integer arithmetic: SQL's
+ *                           PERCENTILE_DISC(num / den).  num = 0 is the minimum, num = den the maximum, 1/2 over N = 4 is s[1].
+ *   out_counts[g*n_q + q]   the number of columns of X holding exactly that value
+ * N_g == 0 gives value 0 and count 0 for every q.  Every element of the three arrays is written.
+ * A column's value and the ORDER of the values are fbk_bsi_quantiles': sign ? -magnitude : magnitude with int64 wrap-around (at
+ * depth 64 the order is the wrapped int64's, unlike fbk_count_matrix_minmax's), Base not added, sign and plane bits outside
+ * exists ignored, a set sign over magnitude 0 the value 0, stored zeros take part.
+ * Requests: 1 <= den <= 2^20, num <= den, n_q <= 16; they may repeat and come in any order.  n_q == 0: only out_totals is produced,
+ * no plane is read, out_values / out_counts may be NULL.
+ * Arguments a .. n_shards as fbk_count_matrix_minmax: b == NULL is the one-field form (n_b must be 1), filter == NULL no filter,
+ * bit_depth 0..64, n_a, n_b <= 4096, row lists [n_shards][n_a], [n_shards][n_b], [n_shards], [n_shards]; at most 2^20 shards.
+ * n_shards == 0 writes the empty-group values; n_a * n_b == 0 writes nothing.  Errors (NULL ctx / a / bsi / base_rows / out_totals;
+ * NULL q_num / q_den / out_values / out_counts with n_q > 0; den == 0, den > 2^20, num > den; n_q > 16; n_a or n_b > 4096;
+ * bit_depth > 64; b == NULL with n_b != 1; row indexes beyond a batch; unknown flags; a pinned path beyond its cap; histogram
+ * scratch beyond its bound) are FBK_E_INVALID before any launch, and the context stays usable.
+ * Method: ONE radix select on fbk_bsi_sort's key (bit_depth + 1 bits up to depth 62, 64 bits at 63 and 64), whole digits from the
+ * top and the short digit last, whose histograms are kept per (group, request); passes = ceil(key bits / digit) = ceil((bit_depth + 1) / digit)
+ * up to depth 63 and ceil(64 / digit) at 64.  Every pass reads each plane once whatever the number of groups; the ranks are
+ * resolved on the device between the passes; one synchronisation per call.  The result does not depend on the grid, the chunking
+ * or the order of the blocks: every count is a sum of integer adds.  flags picks the kernel path
+ * (featurebase_amd/csrc/fbk_group_quantile_plan.h):
+ *   FBK_GQUANT_GLOBAL  digit 8 bits; 64-bit histograms in device memory, one atomic add per (column, group, live request).  Scratch
+ *                      = n_a * n_b * max(1, n_q) * 2^digit * 8 bytes, not tiled; above 2^30 bytes (2^19 (group, request) pairs)
+ *                      the call is FBK_E_INVALID: block the leading field (fewer A rows per call).
+ *   FBK_GQUANT_LDS     digit 8 bits; 32-bit histograms of ALL the (group, request) pairs in a block's 64 KiB of LDS, so at most
+ *                      64 KiB / (4 * 2^digit) = 64 pairs n_a * n_b * max(1, n_q) (FBK_E_INVALID above); the blocks' partial
+ *                      histograms (at most 2^26 bytes) are summed per bin, then the same scratch as above.
+ *   FBK_GQUANT_AUTO    the LDS path iff n_a * n_b * max(1, n_q) <= 64 (kAutoLdsPairs, fixed from a measured sweep on mutex-like rows:
+ *                      the LDS path was ahead wherever it applies; a single group through FBK_GQUANT_GLOBAL is 14 - 27 x slower).
+ * Rows of batches that are not dense are densified a chunk of shards at a time by fbk_count_matrix_minmax's scatter rule: most =
+ * max(1, min(n_shards, 2^30 / per_shard)) with per_shard = 2^17 * (n_a if A is not dense, n_b if B is not, 1 if the filter is not,
+ * bit_depth + 2 if the BSI batch is not; 2 for it with n_q == 0); chunk = ceil(n_shards / ceil(n_shards / most)); with more than
+ * one chunk every pass densifies them again.
+ * NOT offered: a prepared fbk_query_* form; a fbk_group_* form (quantiles of shards on different devices do not merge: a group
+ * must live on one device); the reference's bisection Percentile (fbk_bsi_percentile) replayed per group.  The reference has no
+ * counterpart: its GroupBy takes Count, Sum and Count(Distinct) only. */
+#define FBK_GQUANT_AUTO   0u /* the library chooses the kernel path by the shape */
+#define FBK_GQUANT_LDS    1u /* pin the LDS-histogram path; FBK_E_INVALID when the (group, request) pairs exceed its cap */
+#define FBK_GQUANT_GLOBAL 2u /* pin the device-memory histogram path */
+int32_t fbk_count_matrix_quantiles(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b,
+                                   const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
+                                   const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, uint32_t n_shards,
+                                   const uint32_t* q_num, const uint32_t* q_den, uint32_t n_q, uint32_t flags, int64_t* out_values,
+                                   uint64_t* out_counts, uint64_t* out_totals);
+
 /* ---- GroupBy(..., having=, sort=, offset=, limit=): only the selected groups leave the device -----
  * executeGroupBy's tail (executor.go:3176-3459: ApplyConditionToGroupCounts / satisfiesCondition :3787-3916, groupCountSorter and
  * getSorter :3096-3162, sort.Stable :3409, applyLimitAndOffsetToGroupByResult :3441-3459) applied to the totals of a GroupBy call

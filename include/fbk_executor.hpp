@@ -57,6 +57,14 @@ struct GroupMinMax {  // a GroupBy record with the Min / Max of an int field (SQ
     return Group == o.Group && Count == o.Count && Min == o.Min && Max == o.Max && MinCount == o.MinCount && MaxCount == o.MaxCount;
   }
 };
+struct GroupQuantiles {  // a GroupBy record with percentiles of an int field (SQL PERCENTILE_DISC(x, p) ... GROUP BY): Executor::GroupByQuantiles
+  std::vector<FieldRow> Group;
+  uint64_t Count = 0;            // |group ∩ filter|, as GroupBy's
+  uint64_t N = 0;                // the columns of the group that have a value
+  std::vector<int64_t> Values;   // per fraction: the value at rank max(1, ceil(N * num / den)) - 1, Base added; 0 when N == 0
+  std::vector<uint64_t> Counts;  // per fraction: the columns holding exactly that value; 0 when N == 0
+  bool operator==(const GroupQuantiles& o) const { return Group == o.Group && Count == o.Count && N == o.N && Values == o.Values && Counts == o.Counts; }
+};
 struct GroupByCondition {  // having=Condition(count|sum <op> v): satisfiesCondition (executor.go:3787-3901)
   std::string subject;    // "count" | "sum"
   uint32_t op = 0;        // FBK_HAVING_*
@@ -1020,7 +1028,70 @@ class Executor {
     std::unique_ptr<RowSet> prefix;
     if (filter) prefix.reset(new RowSet(eval(*filter)));
     std::vector<FieldRow> group;
-    minmax_rec(fields, 0, prefix.get(), agg_field, limit, group, out);
+    last_levels_rec(fields, 0, prefix.get(), group, [&](size_t level, const Index::SetField& fa, const std::vector<uint32_t>& rows_a, const Index::SetField* fb,
+                                                       const std::vector<uint32_t>* rows_b, const RowSet* pre, const std::vector<uint64_t>& tot) {
+      const size_t na = fa.row_ids.size(), nb = fb ? fb->row_ids.size() : 1;
+      std::vector<int64_t> mins, maxs;
+      std::vector<uint64_t> cmin, cmax;
+      minmax_matrix(agg_field, fa, rows_a, fb, rows_b, pre, mins, maxs, cmin, cmax);
+      for (size_t i = 0; i < na; ++i)
+        for (size_t j = 0; j < nb; ++j) {
+          const size_t k = i * nb + j;
+          if (!tot[k]) continue;  // groupByIterator.Next skips Count == 0 (executor.go:8905-8913)
+          GroupMinMax g;
+          g.Group = group;
+          g.Group.push_back({fields[level], fa.row_ids[i]});
+          if (fb) g.Group.push_back({fields[level + 1], fb->row_ids[j]});
+          g.Count = tot[k], g.Min = mins[k], g.Max = maxs[k], g.MinCount = cmin[k], g.MaxCount = cmax[k];
+          out.push_back(std::move(g));
+          if (limit && out.size() >= limit) return false;
+        }
+      return true;
+    });
+    return out;
+  }
+
+  // GroupBy(Rows(f0), Rows(f1), ..., filter) with percentiles of an int field per group — SQL's SELECT f0, f1, PERCENTILE_DISC(x, p)
+  // ... GROUP BY f0, f1 (the reference evaluates it row by row on the host).  The groups are GroupBy's (Count = |group ∩ filter|,
+  // Count == 0 skipped, odometer order, limit).  Per fraction (num, den): with s the ascending values of the field over group ∩
+  // filter and N their number, s[max(1, ceil(N * num / den)) - 1] with Base added, and the number of columns holding it; a group
+  // without a value has N == 0 and zeros.  At most 16 fractions, den <= 2^20.  The last one or two levels take one
+  // fbk_count_matrix_quantiles call per block of kSumBlock x kSumBlock rows (rows of the leading field fewer where the call's
+  // histogram scratch asks for it); earlier levels fix their row as GroupByMinMax does.
+  std::vector<GroupQuantiles> GroupByQuantiles(const std::vector<std::string>& fields, const Call* filter, const std::string& agg_field,
+                                               const std::vector<std::pair<uint32_t, uint32_t>>& fractions, uint64_t limit = 0) {
+    if (fields.empty()) throw Error(FBK_E_INVALID, "need at least one child call");  // executor.go:3927
+    if (!idx_.ints_.count(agg_field))
+      throw Error(FBK_E_INVALID, "GroupBy Percentile(field=" + agg_field + "): " +
+                                     (idx_.sets_.count(agg_field) ? "set fields are not supported, only int fields" : "no such int field"));
+    Scope sc(*this, {filter});
+    std::vector<GroupQuantiles> out;
+    if (shards().empty()) return out;
+    std::unique_ptr<RowSet> prefix;
+    if (filter) prefix.reset(new RowSet(eval(*filter)));
+    std::vector<FieldRow> group;
+    const size_t nq = fractions.size();
+    last_levels_rec(fields, 0, prefix.get(), group, [&](size_t level, const Index::SetField& fa, const std::vector<uint32_t>& rows_a, const Index::SetField* fb,
+                                                       const std::vector<uint32_t>* rows_b, const RowSet* pre, const std::vector<uint64_t>& tot) {
+      const size_t na = fa.row_ids.size(), nb = fb ? fb->row_ids.size() : 1;
+      std::vector<int64_t> vals;
+      std::vector<uint64_t> cnts, ns;
+      quantile_matrix(agg_field, fractions, fa, rows_a, fb, rows_b, pre, vals, cnts, ns);
+      for (size_t i = 0; i < na; ++i)
+        for (size_t j = 0; j < nb; ++j) {
+          const size_t k = i * nb + j;
+          if (!tot[k]) continue;  // groupByIterator.Next skips Count == 0 (executor.go:8905-8913)
+          GroupQuantiles g;
+          g.Group = group;
+          g.Group.push_back({fields[level], fa.row_ids[i]});
+          if (fb) g.Group.push_back({fields[level + 1], fb->row_ids[j]});
+          g.Count = tot[k], g.N = ns[k];
+          g.Values.assign(vals.begin() + k * nq, vals.begin() + (k + 1) * nq), g.Counts.assign(cnts.begin() + k * nq, cnts.begin() + (k + 1) * nq);
+          out.push_back(std::move(g));
+          if (limit && out.size() >= limit) return false;
+        }
+      return true;
+    });
     return out;
   }
 
@@ -1658,10 +1729,43 @@ class Executor {
           }
       }
   }
-  // GroupByMinMax over fields[level..]: the last one or two levels are one count call and one minmax_matrix; earlier levels
-  // materialise prefix ∩ row as group_by_rec does
-  bool minmax_rec(const std::vector<std::string>& fields, size_t level, const RowSet* prefix, const std::string& agg_field, uint64_t limit,
-                  std::vector<FieldRow>& group, std::vector<GroupMinMax>& out) {
+  // Percentiles of an int field for the last level (fb == nullptr) or the last two levels: fbk_count_matrix_quantiles with the prefix
+  // row (if any) as the filter, in blocks of rows as minmax_matrix; the leading field's block shrinks until the call's histograms
+  // (2 KiB per group and fraction) fit its 2^30-byte scratch.  vals / cnts: [na * nb][fractions], Base added where the group has a
+  // value; ns: [na * nb].
+  void quantile_matrix(const std::string& agg_field, const std::vector<std::pair<uint32_t, uint32_t>>& fractions, const Index::SetField& fa,
+                       const std::vector<uint32_t>& rows_a, const Index::SetField* fb, const std::vector<uint32_t>* rows_b, const RowSet* prefix,
+                       std::vector<int64_t>& vals, std::vector<uint64_t>& cnts, std::vector<uint64_t>& ns) {
+    const Index::IntField& f = idx_.ints_.at(agg_field);
+    std::vector<uint32_t> base = base_rows(f), num, den;
+    for (const auto& fr : fractions) num.push_back(fr.first), den.push_back(fr.second);
+    const size_t n = base.size(), na = fa.row_ids.size(), nb = fb ? fb->row_ids.size() : 1, nq = fractions.size();
+    vals.assign(na * nb * nq, 0), cnts.assign(na * nb * nq, 0), ns.assign(na * nb, 0);
+    const size_t bj_most = std::min(kSumBlock, nb), pairs_most = (size_t(1) << 30) / (8u << 8);  // (FBK_GQUANT_GLOBAL's digit: 8 bits)
+    const size_t bi_most = std::max<size_t>(1, std::min(kSumBlock, pairs_most / (bj_most * std::max<size_t>(1, nq))));
+    for (size_t i0 = 0; i0 < na; i0 += bi_most)
+      for (size_t j0 = 0; j0 < nb; j0 += kSumBlock) {
+        const size_t bi = std::min(bi_most, na - i0), bj = std::min(kSumBlock, nb - j0);
+        const std::vector<uint32_t> ra = row_block(rows_a, n, na, i0, bi);
+        const std::vector<uint32_t> rb = fb ? row_block(*rows_b, n, nb, j0, bj) : std::vector<uint32_t>();
+        std::vector<int64_t> v(bi * bj * nq);
+        std::vector<uint64_t> c(bi * bj * nq), t(bi * bj);
+        check(fbk_count_matrix_quantiles(idx_.ctx_, fa.batch, ra.data(), uint32_t(bi), fb ? fb->batch : nullptr, fb ? rb.data() : nullptr, uint32_t(bj),
+                                         prefix ? prefix->batch() : nullptr, prefix ? prefix->rows().data() : nullptr, f.batch, base.data(), f.bit_depth,
+                                         uint32_t(n), num.data(), den.data(), uint32_t(nq), FBK_GQUANT_AUTO, v.data(), c.data(), t.data()));
+        for (size_t i = 0; i < bi; ++i)
+          for (size_t j = 0; j < bj; ++j) {
+            const size_t k = (i0 + i) * nb + j0 + j, g = i * bj + j;
+            ns[k] = t[g];
+            for (size_t q = 0; q < nq && t[g]; ++q) vals[k * nq + q] = int64_t(uint64_t(v[g * nq + q]) + uint64_t(f.base)), cnts[k * nq + q] = c[g * nq + q];
+          }
+      }
+  }
+  // GroupByMinMax / GroupByQuantiles over fields[level..]: the last one or two levels are one count call (tot = Count per group)
+  // and leaf(level, fa, rows_a, fb, rows_b, prefix, tot), which emits the records and returns false once the limit is reached;
+  // earlier levels materialise prefix ∩ row as group_by_rec does
+  template <class Leaf>
+  bool last_levels_rec(const std::vector<std::string>& fields, size_t level, const RowSet* prefix, std::vector<FieldRow>& group, const Leaf& leaf) {
     const size_t n = shards().size();
     const Index::SetField& fa = idx_.sets_.at(fields[level]);
     const size_t na = fa.row_ids.size();
@@ -1674,9 +1778,9 @@ class Executor {
         bool go;
         if (prefix) {
           RowSet p = setop(FBK_OP_AND, r, *prefix);
-          go = count_rows(p) == 0 ? true : minmax_rec(fields, level + 1, &p, agg_field, limit, group, out);
+          go = count_rows(p) == 0 ? true : last_levels_rec(fields, level + 1, &p, group, leaf);
         } else {
-          go = minmax_rec(fields, level + 1, &r, agg_field, limit, group, out);
+          go = last_levels_rec(fields, level + 1, &r, group, leaf);
         }
         group.pop_back();
         if (!go) return false;
@@ -1707,22 +1811,7 @@ class Executor {
       for (size_t s = 0; s < n; ++s)
         for (size_t i = 0; i < na; ++i) tot[i] += c[s * na + i];
     }
-    std::vector<int64_t> mins, maxs;
-    std::vector<uint64_t> cmin, cmax;
-    minmax_matrix(agg_field, fa, rows_a, fb, fb ? &rows_b : nullptr, prefix, mins, maxs, cmin, cmax);
-    for (size_t i = 0; i < na; ++i)
-      for (size_t j = 0; j < nb; ++j) {
-        const size_t k = i * nb + j;
-        if (!tot[k]) continue;  // groupByIterator.Next skips Count == 0 (executor.go:8905-8913)
-        GroupMinMax g;
-        g.Group = group;
-        g.Group.push_back({fields[level], fa.row_ids[i]});
-        if (fb) g.Group.push_back({fields[level + 1], fb->row_ids[j]});
-        g.Count = tot[k], g.Min = mins[k], g.Max = maxs[k], g.MinCount = cmin[k], g.MaxCount = cmax[k];
-        out.push_back(std::move(g));
-        if (limit && out.size() >= limit) return false;
-      }
-    return true;
+    return leaf(level, fa, rows_a, fb, fb ? &rows_b : nullptr, prefix, tot);
   }
   // fields[level..]: the last three levels are one count-cube call; with an aggregate the last two are one count-matrix-sum /
   // -distinct call; earlier levels materialise prefix ∩ row (gbi.rows[i].row.Intersect(gbi.rows[i-1].row), executor.go:8829-8834)
