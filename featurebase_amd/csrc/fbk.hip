@@ -33,6 +33,7 @@
 #include "fbk_moments.hip.h"
 #include "fbk_compare.hip.h"
 #include "fbk_matrix_cube.hip.h"
+#include "fbk_group_walk.hip.h"
 #include "fbk_matrix_distinct.hip.h"
 #include "fbk_matrix_minmax.hip.h"
 #include "fbk_extract.hip.h"
@@ -44,6 +45,8 @@
 #include "fbk_expr_topk.hip.h"
 #include "fbk_group_select.hip.h"
 #include "fbk_wire_kernels.hip.h"
+#undef FBK_GROUP_PARAMS  // fbk_group_walk.hip.h's pair: for the kernels' signatures only
+#undef FBK_GROUP_ARGS
 
 using fbk::Slot;
 using fbk::u64;
@@ -1395,6 +1398,7 @@ int32_t fbk_count_range(fbk_ctx* ctx, const fbk_batch* batch, const uint32_t* ro
 #include "fbk_output.inc"
 #include "fbk_plan_api.inc"
 #include "fbk_dense_operands.inc"
+#include "fbk_group_field.inc"       // the operands of the GroupBy aggregates over an int field
 #include "fbk_query_api.inc"         // shared helpers (check_rows, FilterArgs, RowRecords), Rows / Flip / Shift / compaction
 #include "fbk_fold_api.inc"          // the n-way folds: FoldPlan
 #include "fbk_bsi_api.inc"           // the BSI calls: BsiRangePlan, BsiSumPlan

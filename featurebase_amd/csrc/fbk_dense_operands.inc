@@ -6,18 +6,14 @@
 // (k_densify_rows) into scratch, and the kernel reads the scratch through a list of the rows' places in it.  DenseOperands decides
 // which, builds the lists, lays the operands of a call out in ONE scratch buffer in the order they were added, and hands a call
 // site the (arena, rows) pair its kernel takes for the chunk [s0, s0 + ns).  How many shards a chunk holds is the caller's own
-// arithmetic (even_chunk with its budget and per-shard term: fbk.h documents it per call).
+// arithmetic (fbk_dense_policy.h's even_chunk with its budget and per-shard term: fbk.h documents it per call).  The GroupBy
+// aggregates over an int field share one frame on top of it (fbk_group_field.inc).
 
 namespace {
 
-constexpr uint64_t kDenseRowBytes = uint64_t(fbk::kSlots) * 8192;
-
-// Shards per chunk: at most budget / per_shard of them, and the shards dealt evenly over the chunks that takes (no short last chunk).
-uint32_t even_chunk(uint32_t n_shards, uint64_t budget, uint64_t per_shard) {
-  const uint64_t most = per_shard ? std::max<uint64_t>(1, std::min<uint64_t>(n_shards, budget / per_shard)) : n_shards;
-  const uint64_t passes = (n_shards + most - 1) / most;
-  return uint32_t((n_shards + passes - 1) / passes);
-}
+using fbk::even_chunk;  // fbk_dense_policy.h, as the size of a dense row
+using fbk::kDenseRowBytes;
+static_assert(kDenseRowBytes == uint64_t(fbk::kSlots) * 8192, "");
 
 void densify_launch(fbk_ctx* ctx, const std::vector<fbk::DensifySrc>& srcs) {  // three sources per launch
   for (size_t k0 = 0; k0 < srcs.size(); k0 += 3) {

@@ -1,6 +1,7 @@
 // fbk_dense_policy.h — shape rules of the dense count: which plans take k_icount_dense_resident (plan_icount_dense,
-// fbk_plan_api.inc) and which pairs a block of its persistent grid walks, in which order.  Plain C++, HIP not needed:
-// scripts/dense_footprint_check.cpp compiles it on its own.
+// fbk_plan_api.inc) and which pairs a block of its persistent grid walks, in which order; the size of a dense row and how many
+// shards of densified rows a chunk of scratch holds (even_chunk).  Plain C++, HIP not needed: scripts/dense_footprint_check.cpp and
+// the plan checks under tests/cpp compile it on their own.
 #pragma once
 #include <stdint.h>
 
@@ -22,6 +23,16 @@ FBK_HD inline uint32_t resident_pair(uint32_t bid, uint32_t grid, uint32_t it, u
 }
 
 constexpr uint64_t kDenseRowBytes = 16ull * 8192;  // one dense row: 16 bitmap containers
+
+// Shards per densify chunk (fbk_dense_operands.inc): at most budget / per_shard of them, and the shards dealt evenly over the chunks
+// that takes (no short last chunk).  The callers' rules (fbk_minmax_plan.h, fbk_group_quantile_plan.h, fbk_moments_plan.h) and
+// their stand-alone checks call it with their own budget.
+inline uint32_t even_chunk(uint32_t n_shards, uint64_t budget, uint64_t per_shard) {
+  if (n_shards == 0 || per_shard == 0) return n_shards;
+  const uint64_t fit = budget / per_shard, most = fit < 1 ? 1 : fit < n_shards ? fit : n_shards;
+  const uint64_t chunks = (n_shards + most - 1) / most;
+  return uint32_t((n_shards + chunks - 1) / chunks);
+}
 
 // Upper bound of the bytes one dense count of a plan reads, from the shape alone (the row lists are not looked at): a plan
 // of n_pairs pairs touches at most min(n_pairs, rows) distinct rows of each batch, and at most min(2 * n_pairs, rows) of a

@@ -1,14 +1,14 @@
 // fbk_group_quantile.hip.h — GroupBy with a percentile of an int field per group (SQL SELECT a, b, PERCENTILE_DISC(x, p) ... GROUP BY
 // a, b) for all (A row, B row) groups at once, for DENSE operands: ONE radix select (fbk_quantile.hip.h's, most significant digit
-// first, on fbk_sort.hip.h's key: ascending, stored zeros take part) whose histograms are kept PER GROUP, on k_minmax_scatter's walk.
+// first, on fbk_sort.hip.h's key: ascending, stored zeros take part) whose histograms are kept PER GROUP, on group_column_walk
+// (fbk_group_walk.hip.h).
 //
-//   k_gquant_hist_global / _lds   a wavefront walks 64-column words (lane = column): valid = exists & F is wave-uniform and a word
-//                     without a column is skipped; the 64 x 64 transpose of the planes gives the lane its key, transposes of 64 A
-//                     rows' and 64 B rows' words its membership masks.  For every (i, j) of its masks and every request q of that
-//                     group the lane compares the key's bits above the current digit with slot[group][q].prefix and, where they are
-//                     equal, adds 1 to hist[group][q][digit].  Pass 0 has no prefix and ONE histogram per group, shared by its
-//                     requests; its sum is the group's N.  A group without a column and a request that is done carry a prefix no
-//                     key has.  Every pass reads each plane once whatever the number of groups.
+//   k_gquant_hist_global / _lds   the walk's magnitude and the sign give the lane its column's key; every column of exists & F takes
+//                     part.  For every (i, j) of its masks and every request q of that group the lane compares the key's bits
+//                     above the current digit with slot[group][q].prefix and, where they are equal, adds 1 to
+//                     hist[group][q][digit].  Pass 0 has no prefix and ONE histogram per group, shared by its requests; its sum
+//                     is the group's N.  A group without a column and a request that is done carry a prefix no key has.  Every
+//                     pass reads each plane once whatever the number of groups.
 //        GLOBAL       64-bit counters in device memory, atomicAdd (global_atomic_add_x2, no return): for many groups, where the
 //                     adds spread over many lines.
 //        LDS          32-bit counters of ALL the call's (group, request) pairs in the block's LDS (at most 64 KiB, dynamic); every
@@ -22,13 +22,12 @@
 // Every count is a sum of integer adds: the result does not depend on the grid, the chunking or the order of the blocks.
 #pragma once
 #include "fbk_group_quantile_plan.h"
+#include "fbk_group_walk.hip.h"
 #include "fbk_quantile.hip.h"
 
 namespace fbk {
 
-constexpr uint32_t kGquantWords = 16;    // 64-column words per wavefront unit (a 128-byte line of every row)
-constexpr u64 kGquantNoPrefix = ~0ull;   // no key >> (1 or more) equals it: an empty group's requests
-constexpr uint32_t kGquantBlocks = 2048;  // most blocks of a GLOBAL launch
+constexpr u64 kGquantNoPrefix = ~0ull;  // no key >> (1 or more) equals it: an empty group's requests
 
 struct GquantSlot {  // a request of a group on its way down the digits
   u64 prefix;        // the key's digits so far
@@ -46,96 +45,53 @@ __device__ __forceinline__ void gquant_add(u64* p) { atomicAdd(reinterpret_cast<
 __device__ __forceinline__ void gquant_add(uint32_t* p) { atomicAdd(p, 1u); }
 
 // n_h == 0: pass 0, hist[group][bins]; else hist[group][n_h][bins] and slots[group][n_h].  Counter: u64 (device memory) or uint32_t
-// (LDS).  arenaB == nullptr: the one-field form (nB == 1).  rowsS[shard] = exists row, + 1 sign, + 2 + p plane p.
+// (LDS).
 template <class Counter>
-__device__ __forceinline__ void gquant_walk(const uint8_t* __restrict__ arenaA, const uint32_t* __restrict__ rowsA, uint32_t nA,
-                                            const uint8_t* __restrict__ arenaB, const uint32_t* __restrict__ rowsB, uint32_t nB,
-                                            const uint8_t* __restrict__ arenaF, const uint32_t* __restrict__ rowsF,
-                                            const uint8_t* __restrict__ arenaS, const uint32_t* __restrict__ rowsS, uint32_t depth,
-                                            uint32_t n_shards, uint32_t shift, uint32_t wbits, uint32_t dbits, uint32_t n_h,
+__device__ __forceinline__ void gquant_walk(FBK_GROUP_PARAMS, uint32_t shift, uint32_t wbits, uint32_t dbits, uint32_t n_h,
                                             const GquantSlot* __restrict__ slots, Counter* hist) {
   const SortKey sk = gquant_key(depth);
   const int lane = threadIdx.x & 63;
-  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  constexpr uint64_t kRowWords = (uint64_t)kSlots * 1024;
-  constexpr uint32_t kUnits = kRowWords / kGquantWords;
-  const uint32_t wb = (nB + 63) / 64;
   const uint32_t bins = 1u << dbits, pshift = n_h ? shift + wbits : 0;  // (n_h != 0: shift + wbits < 64); the digit: wbits <= dbits bits
-  const TrConst tc = tr_const(lane);
-  const uint64_t units = (uint64_t)n_shards * kUnits;
-  for (uint64_t u = (uint64_t)blockIdx.x * 4 + wv; u < units; u += (uint64_t)gridDim.x * 4) {
-    const uint32_t shard = uint32_t(u / kUnits), w0 = uint32_t(u % kUnits) * kGquantWords;
-    const u64* ex = reinterpret_cast<const u64*>(arenaS) + (uint64_t)rowsS[shard] * kRowWords;
-    const u64* fl = arenaF ? reinterpret_cast<const u64*>(arenaF) + (uint64_t)rowsF[shard] * kRowWords : nullptr;
-    const uint32_t* ra = rowsA + (uint64_t)shard * nA;
-    const uint32_t* rb = arenaB ? rowsB + (uint64_t)shard * nB : nullptr;
-    for (uint32_t w = w0; w < w0 + kGquantWords; ++w) {
-      u64 valid = ex[w];  // (wave-uniform)
-      if (fl) valid &= fl[w];
-      if (valid == 0) continue;
-      // lane p holds plane p's word; transposed, lane c holds the magnitude of column c.  depth == 0 reads neither plane nor sign
-      const u64 pw = (uint32_t)lane < depth ? ex[(uint64_t)(2 + lane) * kRowWords + w] : 0ull;
-      const u64 mag = wave_transpose64(pw, tc);
-      const bool neg = depth && ((ex[kRowWords + w] >> lane) & 1);
-      const u64 key = sort_key(neg ? 0ull - mag : mag, sk);
-      const uint32_t digit = (uint32_t)(key >> shift) & ((1u << wbits) - 1);
-      const u64 kp = key >> pshift;
-      const bool on = (valid >> lane) & 1;
-      for (uint32_t wj = 0; wj < wb; ++wj) {
-        u64 bm = 1;  // the one-field form: every column is in "B row 0"
-        if (rb) {
-          const uint32_t j = wj * 64 + (uint32_t)lane;
-          const u64 bw = j < nB ? reinterpret_cast<const u64*>(arenaB)[(uint64_t)rb[j] * kRowWords + w] : 0ull;
-          bm = wave_transpose64(bw, tc);
-        }
-        const bool onb = on && bm != 0;
-        if (__ballot(onb) == 0) continue;
-        for (uint32_t wa = 0; wa * 64 < nA; ++wa) {
-          const uint32_t ia = wa * 64 + (uint32_t)lane;
-          const u64 aw = ia < nA ? reinterpret_cast<const u64*>(arenaA)[(uint64_t)ra[ia] * kRowWords + w] : 0ull;
-          u64 am = wave_transpose64(aw, tc);
-          if (!onb) am = 0;
-          while (am) {
-            const uint32_t ka = (uint32_t)__builtin_ctzll(am);
-            am &= am - 1;
-            for (u64 b = bm; b; b &= b - 1) {
-              const uint64_t cell = (uint64_t)(wa * 64 + ka) * nB + wj * 64 + (uint32_t)__builtin_ctzll(b);  // < nA * nB: the masks' bits are rows
-              if (n_h == 0) {
-                gquant_add(hist + cell * bins + digit);
-              } else {
-                for (uint32_t q = 0; q < n_h; ++q)
-                  if (slots[cell * n_h + q].prefix == kp) gquant_add(hist + ((cell * n_h + q) << dbits) + digit);
-              }
-            }
+  uint32_t digit = 0;  // of the lane's column's key
+  u64 kp = 0;          // the key's bits above the digit
+  group_column_walk<false>(
+      FBK_GROUP_ARGS, 0, nA,
+      [&](const u64* exw, bool valid, u64 mag) {
+        const bool neg = depth && ((exw[kGroupRowWords] >> lane) & 1);  // (depth == 0 reads neither plane nor sign)
+        const u64 key = sort_key(neg ? 0ull - mag : mag, sk);
+        digit = (uint32_t)(key >> shift) & ((1u << wbits) - 1);
+        kp = key >> pshift;
+        return valid;
+      },
+      [&](uint32_t a_row, uint32_t wj, u64 bm) {
+        for (u64 b = bm; b; b &= b - 1) {
+          const uint64_t cell = (uint64_t)a_row * nB + wj * 64 + (uint32_t)__builtin_ctzll(b);  // < nA * nB: the masks' bits are rows
+          if (n_h == 0) {
+            gquant_add(hist + cell * bins + digit);
+          } else {
+            for (uint32_t q = 0; q < n_h; ++q)
+              if (slots[cell * n_h + q].prefix == kp) gquant_add(hist + ((cell * n_h + q) << dbits) + digit);
           }
         }
-      }
-    }
-  }
+      });
 }
 
-#define FBK_GQUANT_PARAMS                                                                                                                     \
-  const uint8_t *__restrict__ arenaA, const uint32_t *__restrict__ rowsA, uint32_t nA, const uint8_t *__restrict__ arenaB,                   \
-      const uint32_t *__restrict__ rowsB, uint32_t nB, const uint8_t *__restrict__ arenaF, const uint32_t *__restrict__ rowsF,                \
-      const uint8_t *__restrict__ arenaS, const uint32_t *__restrict__ rowsS, uint32_t depth, uint32_t n_shards, uint32_t shift,             \
-      uint32_t wbits,                                                                                                                       \
-      uint32_t dbits, uint32_t n_h, const GquantSlot *__restrict__ slots
-#define FBK_GQUANT_ARGS arenaA, rowsA, nA, arenaB, rowsB, nB, arenaF, rowsF, arenaS, rowsS, depth, n_shards, shift, wbits, dbits, n_h, slots
-
 // hist: [nA * nB][max(1, n_h)][1 << dbits], zeroed by the caller
-__global__ void __launch_bounds__(256) k_gquant_hist_global(FBK_GQUANT_PARAMS, u64* hist) { gquant_walk<u64>(FBK_GQUANT_ARGS, hist); }
+__global__ void __launch_bounds__(256) k_gquant_hist_global(FBK_GROUP_PARAMS, uint32_t shift, uint32_t wbits, uint32_t dbits, uint32_t n_h,
+                                                            const GquantSlot* __restrict__ slots, u64* hist) {
+  gquant_walk<u64>(FBK_GROUP_ARGS, shift, wbits, dbits, n_h, slots, hist);
+}
 
 // part: [gridDim.x][n_bins], n_bins = nA * nB * max(1, n_h) << dbits counters = the dynamic LDS of the launch (at most 64 KiB)
-__global__ void __launch_bounds__(256) k_gquant_hist_lds(FBK_GQUANT_PARAMS, uint32_t n_bins, uint32_t* __restrict__ part) {
+__global__ void __launch_bounds__(256) k_gquant_hist_lds(FBK_GROUP_PARAMS, uint32_t shift, uint32_t wbits, uint32_t dbits, uint32_t n_h,
+                                                         const GquantSlot* __restrict__ slots, uint32_t n_bins, uint32_t* __restrict__ part) {
   extern __shared__ __attribute__((aligned(16))) uint32_t gq[];
   for (uint32_t i = threadIdx.x; i < n_bins; i += 256) gq[i] = 0;
   __syncthreads();
-  gquant_walk<uint32_t>(FBK_GQUANT_ARGS, gq);
+  gquant_walk<uint32_t>(FBK_GROUP_ARGS, shift, wbits, dbits, n_h, slots, gq);
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < n_bins; i += 256) part[(uint64_t)blockIdx.x * n_bins + i] = gq[i];
 }
-#undef FBK_GQUANT_PARAMS
-#undef FBK_GQUANT_ARGS
 
 // One wavefront per pair = group * max(1, n_q) + q.  hist: the finished pass's (first: [cells][bins], else [pairs][bins]; its digit
 // had wbits bits, the bins beyond are zero).  first:

@@ -2,7 +2,7 @@
 // one call (fbk_group_quantile.hip.h).  Included by fbk.hip after fbk_quantile_api.inc; the argument checks of the operands are
 // fbk_count_matrix_sum's (msum_args_ok).
 //
-// The kernels read dense rows (fbk_dense_operands.inc), a chunk of shards at a time; the path, the digits, the passes, the scratch
+// The kernels read dense rows through GroupFieldOperands (fbk_group_field.inc), a chunk of shards at a time; the path, the digits, the passes, the scratch
 // bound and the chunk are fbk_group_quantile_plan.h's rules.  (fbk.h documents the arithmetic: the tests rely on it.)  A pass is a
 // memset of the histograms, one histogram launch per chunk and k_gquant_resolve; nothing comes back to the host between the passes:
 // the call synchronises once.  With more than one chunk every pass densifies every chunk again.
@@ -26,7 +26,8 @@ int32_t fbk_count_matrix_quantiles(fbk_ctx* ctx, const fbk_batch* a, const uint3
       return fail(FBK_E_INVALID, "count_matrix_quantiles: a request is num / den with 1 <= den <= 2^20 and num <= den");
   if (flags > FBK_GQUANT_GLOBAL) return fail(FBK_E_INVALID, "count_matrix_quantiles: unknown flags");
   if (!ctx || !a || !out_totals) return fail(FBK_E_INVALID, "NULL argument");
-  if (int32_t rc = msum_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
+  const GroupFieldArgs args{a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards};
+  if (int32_t rc = msum_args_ok(args)) return rc;
   if (n_shards > (1u << 20)) return fail(FBK_E_INVALID, "count_matrix_quantiles: at most 2^20 shards per call");
   const uint32_t path = gp::path(n_a, n_b, n_q, flags);
   if (!path)
@@ -45,12 +46,10 @@ int32_t fbk_count_matrix_quantiles(fbk_ctx* ctx, const fbk_batch* a, const uint3
   const uint32_t depth = n_q ? bit_depth : 0;  // n_q == 0: the totals alone, no plane is read (the kernels build the key from the depth)
   const uint32_t passes = gp::passes(depth, dbits);
 
-  DenseOperands ops;
-  const int kA = ops.add(a, rows_a, n_a), kB = ops.add(b, rows_b, n_b), kF = ops.add(filter, rows_f, 1), kS = ops.add(bsi, base_rows, depth + 2, true);
-  const uint32_t chunk = gp::densify_chunk(n_shards, ops.densified_rows());
-  if (chunk != even_chunk(n_shards, gp::kDensifyScratch, kDenseRowBytes * ops.densified_rows()))
-    return fail(FBK_E_HIP, "count_matrix_quantiles: fbk_group_quantile_plan.h and fbk_dense_operands.inc disagree on the densify chunk");
-  if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
+  GroupFieldOperands gf;
+  gf.add(args, depth);
+  const uint32_t chunk = gp::densify_chunk(n_shards, gf.ops.densified_rows());
+  if (int32_t rc = gf.upload(ctx, chunk)) return rc;
   DevBuf hist, slots, result, reqs, part;  // result: totals [width], values [answers], counts [answers]
   HIP_TRY(hist.alloc(ctx, pairs * bins * 8));
   HIP_TRY(slots.alloc(ctx, pairs * sizeof(fbk::GquantSlot)));
@@ -61,31 +60,24 @@ int32_t fbk_count_matrix_quantiles(fbk_ctx* ctx, const fbk_batch* a, const uint3
   const uint32_t* d_req[2] = {nullptr, nullptr};
   if (n_q)
     if (int32_t rc = upload_rows_multi(ctx, {{q_num, n_q, UINT32_MAX}, {q_den, n_q, UINT32_MAX}}, reqs, d_req)) return rc;
-  const uint64_t units_most = uint64_t(chunk) * (fbk::kSlots * 1024 / fbk::kGquantWords);
-  if (path == gp::kLds) HIP_TRY(part.alloc(ctx, std::min<uint64_t>((units_most + 3) / 4, gp::kLdsBlocks) * pairs * bins * 4));
+  const auto lds_grid = [&](uint32_t ns) { return std::min(gf.walk_grid(ns), gp::kLdsBlocks); };
+  if (path == gp::kLds) HIP_TRY(part.alloc(ctx, uint64_t(lds_grid(chunk)) * pairs * bins * 4));
   {
     KernelSpan span(ctx);
     for (uint32_t p = 0; p < passes; ++p) {
       const uint32_t shift = gp::pass_low(depth, dbits, p), wbits = gp::pass_width(depth, dbits, p), n_h = p ? n_q : 0;
       const uint64_t n_bins = (p ? pairs : width) * bins;  // (the LDS path: at most 64 KiB / 4)
       HIP_TRY(hipMemsetAsync(hist.p, 0, n_bins * 8, ctx->stream));
-      for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-        const uint32_t ns = std::min(chunk, n_shards - s0);
-        if (p == 0 || chunk < n_shards) ops.densify(ctx, s0, ns);  // (one chunk: still there for the later passes)
-        const DenseView A = ops.view(kA, s0), B = ops.view(kB, s0), F = ops.view(kF, s0), S = ops.view(kS, s0);
-        const uint64_t units = uint64_t(ns) * (fbk::kSlots * 1024 / fbk::kGquantWords);
-#define FBK_GQUANT_OPERANDS A.arena, A.rows, n_a, B.arena, B.rows, n_b, F.arena, F.rows, S.arena, S.rows, depth, ns, shift, wbits, dbits, n_h, slots.as<fbk::GquantSlot>()
+      gf.for_each_chunk(ctx, p == 0, [&](const GroupFieldViews& v, uint32_t, uint32_t ns) {
         if (path == gp::kLds) {
-          const uint32_t nb = uint32_t(std::min<uint64_t>((units + 3) / 4, gp::kLdsBlocks));
-          hipLaunchKernelGGL(fbk::k_gquant_hist_lds, dim3(nb), dim3(256), n_bins * 4, ctx->stream, FBK_GQUANT_OPERANDS, uint32_t(n_bins), part.as<uint32_t>());
+          const uint32_t nb = lds_grid(ns);
+          gf.launch(fbk::k_gquant_hist_lds, nb, n_bins * 4, ctx, v, ns, shift, wbits, dbits, n_h, slots.as<fbk::GquantSlot>(), uint32_t(n_bins), part.as<uint32_t>());
           hipLaunchKernelGGL(fbk::k_quant_hist_sum, dim3(uint32_t(n_bins / 256), 32), dim3(256), 0, ctx->stream, part.as<uint32_t>(), nb, uint32_t(n_bins),
                              hist.as<u64>());
         } else {
-          const uint32_t nb = uint32_t(std::min<uint64_t>((units + 3) / 4, fbk::kGquantBlocks));
-          hipLaunchKernelGGL(fbk::k_gquant_hist_global, dim3(nb), dim3(256), 0, ctx->stream, FBK_GQUANT_OPERANDS, hist.as<u64>());
+          gf.launch(fbk::k_gquant_hist_global, gf.walk_grid(ns), 0, ctx, v, ns, shift, wbits, dbits, n_h, slots.as<fbk::GquantSlot>(), hist.as<u64>());
         }
-#undef FBK_GQUANT_OPERANDS
-      }
+      });
       hipLaunchKernelGGL(fbk::k_gquant_resolve, dim3(uint32_t((pairs + 3) / 4)), dim3(256), 0, ctx->stream, hist.as<u64>(), uint32_t(width), n_q, dbits, wbits, int(p == 0),
                          int(p + 1 == passes), d_req[0], d_req[1], depth, slots.as<fbk::GquantSlot>(), d_totals, d_values, d_counts);
     }

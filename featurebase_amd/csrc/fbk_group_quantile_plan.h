@@ -5,11 +5,13 @@
 //   lds_pairs_cap()                   the most histograms (groups x max(1, n_q)) the LDS path keeps in a block's 64 KiB;
 //   scratch_bytes(), kScratchBound    the histograms in device memory and the most a call may ask for;
 //   path()                            the path of a call from its shape and its flags (0: the flags / shape are an error);
-//   densify_chunk()                   the shards per walk when an operand goes through DenseOperands (fbk_minmax_plan.h's rule).
+//   densify_chunk()                   the shards per walk when an operand goes through DenseOperands (fbk_dense_policy.h's even_chunk).
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
+
+#include "fbk_dense_policy.h"
 
 namespace fbk_gquant_plan {
 
@@ -77,15 +79,9 @@ inline constexpr uint32_t path(uint64_t n_a, uint64_t n_b, uint32_t n_q, uint32_
                             : 0u;
 }
 
-// Shards per walk: at most 2^30 / (2^17 * R) of them (R = the rows densified per shard), dealt evenly over the fewest walks
-// (fbk_dense_operands.inc's even_chunk, as fbk_minmax_plan.h).
-constexpr uint64_t kDensifyScratch = 1ull << 30, kRowBytes = 1ull << 17;
-inline uint32_t densify_chunk(uint32_t n_shards, uint64_t densified) {
-  if (n_shards == 0 || densified == 0) return n_shards;
-  const uint64_t most = std::max<uint64_t>(1, std::min<uint64_t>(n_shards, kDensifyScratch / (kRowBytes * densified)));
-  const uint64_t walks = (n_shards + most - 1) / most;
-  return uint32_t((n_shards + walks - 1) / walks);
-}
+// Shards per walk: at most 2^30 / (2^17 * R) of them (R = the rows densified per shard), dealt evenly over the fewest walks.
+constexpr uint64_t kDensifyScratch = 1ull << 30;
+inline uint32_t densify_chunk(uint32_t n_shards, uint64_t densified) { return fbk::even_chunk(n_shards, kDensifyScratch, fbk::kDenseRowBytes * densified); }
 
 // SQL PERCENTILE_DISC(num / den) over N >= 1 values: the ascending rank max(1, ceil(N * num / den)) - 1.  num <= den <= 2^20 and
 // N <= 2^40 (2^20 shards of 2^20 columns) keep N * num + den within 2^61.

@@ -216,13 +216,14 @@ int32_t fbk_count_matrix_sum_select(fbk_ctx* ctx, const fbk_batch* a, const uint
   FBK_ENTER(ctx);
   if (!ctx || !a) return fail(FBK_E_INVALID, "NULL argument");
   if (int32_t rc = group_select_args_ok(sel, true, out_cells, out_counts, out_aggs, cap, out_n, out_matched)) return rc;
-  if (int32_t rc = msum_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
-  const uint64_t width = uint64_t(n_a) * n_b;
+  const GroupFieldArgs args{a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards};
+  if (int32_t rc = msum_args_ok(args)) return rc;
+  const uint64_t width = args.width();
   if (n_shards == 0 || width == 0) return FBK_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
   MsumPlan p;
-  if (int32_t rc = msum_prepare(ctx, p, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
+  if (int32_t rc = msum_prepare(ctx, p, args)) return rc;
   if (int32_t rc = msum_enqueue(ctx, p)) return rc;
   // p.result = {sums [width], counts [width]}
   return group_select_locked(ctx, p.result.as<u64>() + width, p.result.as<long long>(), width, *sel, out_cells, out_counts, out_aggs, cap, out_n, out_matched);

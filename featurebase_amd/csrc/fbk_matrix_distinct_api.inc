@@ -49,8 +49,9 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
                                   uint64_t* out_distinct, uint64_t* out_counts) try {
   FBK_ENTER(ctx);
   if (!ctx || !a || !out_distinct) return fail(FBK_E_INVALID, "NULL argument");
-  if (int32_t rc = msum_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
-  const uint64_t width = uint64_t(n_a) * n_b;
+  const GroupFieldArgs args{a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards};
+  if (int32_t rc = msum_args_ok(args)) return rc;
+  const uint64_t width = args.width();
   std::memset(out_distinct, 0, width * 8);
   if (out_counts) std::memset(out_counts, 0, width * 8);
   if (n_shards == 0 || width == 0) return FBK_OK;
@@ -62,10 +63,9 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
   if (int32_t rc = bsi_distinct_device(ctx, bsi, base_rows, n_shards, bit_depth, filter, rows_f, duniq, m)) return rc;
   if (m > 0) {
     // stage 2: operands (densified a chunk of shards at a time), presence tiles
-    DenseOperands ops;
-    const int kA = ops.add(a, rows_a, n_a), kB = ops.add(b, rows_b, n_b), kF = ops.add(filter, rows_f, 1), kS = ops.add(bsi, base_rows, bit_depth + 2, true);
-    const uint32_t chunk = even_chunk(n_shards, kMdistScratch, kDenseRowBytes * ops.densified_rows());
-    if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
+    GroupFieldOperands gf;
+    gf.add(args, bit_depth);
+    if (int32_t rc = gf.upload(ctx, even_chunk(n_shards, kMdistScratch, kDenseRowBytes * gf.ops.densified_rows()))) return rc;
     DevBuf pres, result;
     const MdistTiles t = mdist_tiles(n_a, n_b, m);
     const uint32_t wb = (n_b + 63) / 64, tr = uint32_t(t.tr);
@@ -73,21 +73,13 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
     HIP_TRY(pres.alloc(ctx, uint64_t(t.ta) * wb * tr * 8));
     HIP_TRY(result.alloc(ctx, width * 8));
     HIP_TRY(hipMemsetAsync(result.p, 0, width * 8, ctx->stream));
-    bool densified = false;  // (one chunk: its operands are densified once for all the tiles)
     for (uint32_t a0 = 0; a0 < n_a; a0 += t.ta) {
       const uint32_t na = std::min(t.ta, n_a - a0);
       for (uint64_t r0 = 0; r0 < m64; r0 += tr) {
         HIP_TRY(hipMemsetAsync(pres.p, 0, uint64_t(na) * wb * tr * 8, ctx->stream));
-        for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-          const uint32_t ns = std::min(chunk, n_shards - s0);
-          if (!densified) ops.densify(ctx, s0, ns);
-          densified = chunk == n_shards;
-          const DenseView A = ops.view(kA, s0), B = ops.view(kB, s0), F = ops.view(kF, s0), S = ops.view(kS, s0);
-          const uint64_t units = uint64_t(ns) * (fbk::kSlots * 1024 / fbk::kMdistWords);
-          const uint32_t grid = uint32_t(std::min<uint64_t>((units + 3) / 4, 2048));
-          hipLaunchKernelGGL(fbk::k_mdist_scatter, dim3(grid), dim3(256), 0, ctx->stream, A.arena, A.rows, n_a, a0, na, B.arena, B.rows, n_b, F.arena, F.rows, S.arena, S.rows,
-                             bit_depth, duniq.as<long long>(), uint32_t(m), uint32_t(r0), tr, ns, pres.as<u64>());
-        }
+        gf.for_each_chunk(ctx, a0 == 0 && r0 == 0, [&](const GroupFieldViews& v, uint32_t, uint32_t ns) {
+          gf.launch(fbk::k_mdist_scatter, gf.walk_grid(ns), 0, ctx, v, ns, a0, na, duniq.as<long long>(), uint32_t(m), uint32_t(r0), tr, pres.as<u64>());
+        });
         // popcount: enough parts of the rank range for ~8192 wavefronts
         const uint64_t pairs = uint64_t(na) * wb;
         const uint32_t splits = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(tr / 64, 8192 / pairs)));
@@ -103,7 +95,9 @@ int32_t fbk_count_matrix_distinct(fbk_ctx* ctx, const fbk_batch* a, const uint32
   if (out_counts) {
     // stage 3: the columns of every group, fbk_count_matrix_sum's pass at depth 0
     MsumPlan p;
-    if (int32_t rc = msum_prepare(ctx, p, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, 0, n_shards)) return rc;
+    GroupFieldArgs counts_args = args;
+    counts_args.bit_depth = 0;
+    if (int32_t rc = msum_prepare(ctx, p, counts_args)) return rc;
     if (int32_t rc = msum_enqueue(ctx, p)) return rc;
     if (int32_t rc = msum_read(ctx, p, nullptr, out_counts)) return rc;
   }

@@ -13,7 +13,7 @@
 // Two paths (the rule between them: fbk_minmax_plan.h):
 //  (a) plane descent, lanes = groups — few groups.
 //   k_minmax_descent  grid (unit blocks, 64-group tiles).  A wavefront owns the tile's 64 groups (lane = group) and walks units of
-//                     kMinmaxWords consecutive 64-column words of a shard (grid-stride).  Per word the wave-uniform words — exists
+//                     kGroupWalkWords consecutive 64-column words of a shard (grid-stride).  Per word the wave-uniform words — exists
 //                     & F, sign, the OR of the planes, the planes — come through scalar loads (their addresses are uniform), four
 //                     words (32 bytes) of a row per load: a word at a time every scan step waited on a load of its own; the
 //                     lane forms m = A_i & B_j & valid, neg = m & sign & anymag, pos = m & ~neg and runs the reference's
@@ -31,8 +31,8 @@
 //                     butterfly), no atomics; into the running state when the call takes several chunks of shards; after the last
 //                     one converted to the int64 / count outputs.
 //  (b) per-column scatter, lanes = columns — many groups.
-//   k_minmax_scatter  k_mdist_scatter's walk: the 64 x 64 transpose of the planes gives every lane its column's magnitude,
-//                     transposes of 64 A rows' and 64 B rows' words its membership masks; for each (i, j) of its masks the lane
+//   k_minmax_scatter  group_column_walk (fbk_group_walk.hip.h): a lane's column is negative where the sign is set and the walk's
+//                     magnitude is not 0, and every column of exists & F takes part; for each (i, j) of its masks the lane
 //                     updates the group's two magnitudes of its class in state[groups][4] with 64-bit atomicMax / atomicMin
 //                     (global_atomic_umax_x2 / umin_x2: no compare-and-swap loop).  The state only moves one way, so before each
 //                     atomic the lane reads the magnitude with a relaxed agent-scope load (it bypasses L1) and skips an atomic
@@ -43,17 +43,15 @@
 //                     Work: Σ over columns of |A rows holding it| x |B rows holding it| updates: optimal for mutex-like fields,
 //                     poor for set fields with many rows per column.  Scratch: 48 B per group (768 MiB at 4096 x 4096), not tiled.
 #pragma once
-#include "fbk_bsi_kernels.hip.h"
+#include "fbk_group_walk.hip.h"
 
 namespace fbk {
-
-constexpr uint32_t kMinmaxWords = 16;  // 64-column words per wavefront unit (a 128-byte line of every row)
 
 constexpr uint32_t kMinmaxStep = 4;  // words per step of the descent
 struct alignas(32) MinmaxWords {     // kMinmaxStep consecutive words of a row
   u64 w[kMinmaxStep];
 };
-static_assert(kMinmaxWords % kMinmaxStep == 0, "");
+static_assert(kGroupWalkWords % kMinmaxStep == 0, "");
 
 struct MinmaxPartial {  // 64 bytes
   u64 mag[4];           // maxmag_neg, minmag_neg, minmag_pos, maxmag_pos
@@ -89,18 +87,13 @@ __device__ __forceinline__ void mm_write(const u64* mag, bool pos_any, u64 c_max
 }
 
 // ---- (a) plane descent ---------------------------------------------------------------------------------------------------------
-// grid (unit blocks, ceil(nA * nB / 64)).  arenaB == nullptr: the one-field form (nB == 1).  rowsS[shard] = exists row, + 1 sign,
-// + 2 + p plane p.  partial: [gridDim.x][gridDim.y][64].
-__global__ void __launch_bounds__(256) k_minmax_descent(const uint8_t* __restrict__ arenaA, const uint32_t* __restrict__ rowsA, uint32_t nA,
-                                                        const uint8_t* __restrict__ arenaB, const uint32_t* __restrict__ rowsB, uint32_t nB,
-                                                        const uint8_t* __restrict__ arenaF, const uint32_t* __restrict__ rowsF,
-                                                        const uint8_t* __restrict__ arenaS, const uint32_t* __restrict__ rowsS, uint32_t depth,
-                                                        uint32_t n_shards, MinmaxPartial* __restrict__ partial) {
+// grid (unit blocks, ceil(nA * nB / 64)).  partial: [gridDim.x][gridDim.y][64].
+__global__ void __launch_bounds__(256) k_minmax_descent(FBK_GROUP_PARAMS, MinmaxPartial* __restrict__ partial) {
   __shared__ u64 sh[3][8][64];
   const int lane = threadIdx.x & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   constexpr uint64_t kRowWords = (uint64_t)kSlots * 1024;  // u64 words of a row
-  constexpr uint32_t kUnits = kRowWords / kMinmaxWords;    // units per shard
+  constexpr uint32_t kUnits = kRowWords / kGroupWalkWords;  // units per shard
   const uint32_t cell = blockIdx.y * 64 + (uint32_t)lane;
   const bool live = cell < nA * nB;
   const uint32_t i = live ? cell / nB : 0, j = live ? cell % nB : 0;
@@ -108,12 +101,12 @@ __global__ void __launch_bounds__(256) k_minmax_descent(const uint8_t* __restric
   // the wave's units (shard, unit of the shard), grid-stride, in 32-bit counters: the grid is at most 2048 x 4 waves (fbk_minmax_plan.h)
   for (uint32_t uu = blockIdx.x * 4 + wv, shard = uu / kUnits; shard < n_shards; uu += gridDim.x * 4, shard += uu / kUnits) {
     uu %= kUnits;
-    const uint32_t w0 = uu * kMinmaxWords;
+    const uint32_t w0 = uu * kGroupWalkWords;
     const u64* ex = reinterpret_cast<const u64*>(arenaS) + (uint64_t)rowsS[shard] * kRowWords;  // (wave-uniform, as fl and every ex[...] below)
     const u64* fl = arenaF ? reinterpret_cast<const u64*>(arenaF) + (uint64_t)rowsF[shard] * kRowWords : nullptr;
     const u64* pa = reinterpret_cast<const u64*>(arenaA) + (uint64_t)rowsA[(uint64_t)shard * nA + i] * kRowWords;
     const u64* pb = arenaB ? reinterpret_cast<const u64*>(arenaB) + (uint64_t)rowsB[(uint64_t)shard * nB + j] * kRowWords : nullptr;
-    for (uint32_t w = w0; w < w0 + kMinmaxWords; w += kMinmaxStep) {
+    for (uint32_t w = w0; w < w0 + kGroupWalkWords; w += kMinmaxStep) {
       // kMinmaxStep words at a time: one 32-byte scalar load per uniform row and step, and four independent scans per lane
       const MinmaxWords e = *reinterpret_cast<const MinmaxWords*>(ex + w);
       u64 valid[kMinmaxStep], m[kMinmaxStep], many = 0;
@@ -221,88 +214,43 @@ __global__ void __launch_bounds__(256) k_minmax_init(u64* __restrict__ state, u6
 
 // kHolders == false: the magnitudes (state is updated); true: the holders of the final magnitudes (state is read, counts updated)
 template <bool kHolders>
-__device__ __forceinline__ void minmax_walk(const uint8_t* __restrict__ arenaA, const uint32_t* __restrict__ rowsA, uint32_t nA,
-                                            const uint8_t* __restrict__ arenaB, const uint32_t* __restrict__ rowsB, uint32_t nB,
-                                            const uint8_t* __restrict__ arenaF, const uint32_t* __restrict__ rowsF,
-                                            const uint8_t* __restrict__ arenaS, const uint32_t* __restrict__ rowsS, uint32_t depth,
-                                            uint32_t n_shards, u64* state, u64* counts) {
+__device__ __forceinline__ void minmax_walk(FBK_GROUP_PARAMS, u64* state, u64* counts) {
   const int lane = threadIdx.x & 63;
-  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  constexpr uint64_t kRowWords = (uint64_t)kSlots * 1024;
-  constexpr uint32_t kUnits = kRowWords / kMinmaxWords;
-  const uint32_t wb = (nB + 63) / 64;
-  const TrConst tc = tr_const(lane);
-  const uint64_t units = (uint64_t)n_shards * kUnits;
-  for (uint64_t u = (uint64_t)blockIdx.x * 4 + wv; u < units; u += (uint64_t)gridDim.x * 4) {
-    const uint32_t shard = uint32_t(u / kUnits), w0 = uint32_t(u % kUnits) * kMinmaxWords;
-    const u64* ex = reinterpret_cast<const u64*>(arenaS) + (uint64_t)rowsS[shard] * kRowWords;
-    const u64* fl = arenaF ? reinterpret_cast<const u64*>(arenaF) + (uint64_t)rowsF[shard] * kRowWords : nullptr;
-    const uint32_t* ra = rowsA + (uint64_t)shard * nA;
-    const uint32_t* rb = arenaB ? rowsB + (uint64_t)shard * nB : nullptr;
-    for (uint32_t w = w0; w < w0 + kMinmaxWords; ++w) {
-      u64 valid = ex[w];  // (wave-uniform)
-      if (fl) valid &= fl[w];
-      if (valid == 0) continue;
-      // lane p holds plane p's word; transposed, lane c holds the magnitude of column c
-      const u64 pw = (uint32_t)lane < depth ? ex[(uint64_t)(2 + lane) * kRowWords + w] : 0ull;
-      const u64 mag = wave_transpose64(pw, tc);
-      const bool isneg = ((ex[kRowWords + w] >> lane) & 1) && mag != 0;
-      const bool on = (valid >> lane) & 1;
-      const int hi = isneg ? 0 : 3, lo = isneg ? 1 : 2;  // the class's maxmag / minmag
-      for (uint32_t wj = 0; wj < wb; ++wj) {
-        u64 bm = 1;  // the one-field form: every column is in "B row 0"
-        if (rb) {
-          const uint32_t j = wj * 64 + (uint32_t)lane;
-          const u64 bw = j < nB ? reinterpret_cast<const u64*>(arenaB)[(uint64_t)rb[j] * kRowWords + w] : 0ull;
-          bm = wave_transpose64(bw, tc);
-        }
-        const bool onb = on && bm != 0;
-        if (__ballot(onb) == 0) continue;
-        for (uint32_t wa = 0; wa * 64 < nA; ++wa) {
-          const uint32_t ia = wa * 64 + (uint32_t)lane;
-          const u64 aw = ia < nA ? reinterpret_cast<const u64*>(arenaA)[(uint64_t)ra[ia] * kRowWords + w] : 0ull;
-          u64 am = wave_transpose64(aw, tc);
-          if (!onb) am = 0;
-          while (am) {
-            const uint32_t ka = (uint32_t)__builtin_ctzll(am);
-            am &= am - 1;
-            for (u64 b = bm; b; b &= b - 1) {
-              const uint64_t cell = (uint64_t)(wa * 64 + ka) * nB + wj * 64 + (uint32_t)__builtin_ctzll(b);
-              u64* st = state + cell * 4;
-              if constexpr (!kHolders) {
-                if (mag > __hip_atomic_load(st + hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                  atomicMax(reinterpret_cast<unsigned long long*>(st + hi), (unsigned long long)mag);
-                if (mag < __hip_atomic_load(st + lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                  atomicMin(reinterpret_cast<unsigned long long*>(st + lo), (unsigned long long)mag);
-              } else {
-                const bool neg_any = st[0] >= 1, pos_any = st[2] <= st[3];
-                const bool is_min = neg_any ? (isneg && mag == st[0]) : (!isneg && mag == st[2]);
-                const bool is_max = pos_any ? (!isneg && mag == st[3]) : (isneg && mag == st[1]);
-                if (is_min) atomicAdd(reinterpret_cast<unsigned long long*>(counts + cell * 2), 1ull);
-                if (is_max) atomicAdd(reinterpret_cast<unsigned long long*>(counts + cell * 2 + 1), 1ull);
-              }
-            }
+  u64 mag = 0;                // of the lane's column
+  bool isneg = false;         // its class: the sign is set and mag != 0
+  int hi = 3, lo = 2;         // the class's maxmag / minmag
+  group_column_walk<false>(
+      FBK_GROUP_ARGS, 0, nA,
+      [&](const u64* exw, bool valid, u64 m) {
+        mag = m;
+        isneg = ((exw[kGroupRowWords] >> lane) & 1) && mag != 0;
+        hi = isneg ? 0 : 3, lo = isneg ? 1 : 2;
+        return valid;
+      },
+      [&](uint32_t a_row, uint32_t wj, u64 bm) {
+        for (u64 b = bm; b; b &= b - 1) {
+          const uint64_t cell = (uint64_t)a_row * nB + wj * 64 + (uint32_t)__builtin_ctzll(b);
+          u64* st = state + cell * 4;
+          if constexpr (!kHolders) {
+            if (mag > __hip_atomic_load(st + hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+              atomicMax(reinterpret_cast<unsigned long long*>(st + hi), (unsigned long long)mag);
+            if (mag < __hip_atomic_load(st + lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+              atomicMin(reinterpret_cast<unsigned long long*>(st + lo), (unsigned long long)mag);
+          } else {
+            const bool neg_any = st[0] >= 1, pos_any = st[2] <= st[3];
+            const bool is_min = neg_any ? (isneg && mag == st[0]) : (!isneg && mag == st[2]);
+            const bool is_max = pos_any ? (!isneg && mag == st[3]) : (isneg && mag == st[1]);
+            if (is_min) atomicAdd(reinterpret_cast<unsigned long long*>(counts + cell * 2), 1ull);
+            if (is_max) atomicAdd(reinterpret_cast<unsigned long long*>(counts + cell * 2 + 1), 1ull);
           }
         }
-      }
-    }
-  }
+      });
 }
 
-__global__ void __launch_bounds__(256) k_minmax_scatter(const uint8_t* __restrict__ arenaA, const uint32_t* __restrict__ rowsA, uint32_t nA,
-                                                        const uint8_t* __restrict__ arenaB, const uint32_t* __restrict__ rowsB, uint32_t nB,
-                                                        const uint8_t* __restrict__ arenaF, const uint32_t* __restrict__ rowsF,
-                                                        const uint8_t* __restrict__ arenaS, const uint32_t* __restrict__ rowsS, uint32_t depth,
-                                                        uint32_t n_shards, u64* state) {
-  minmax_walk<false>(arenaA, rowsA, nA, arenaB, rowsB, nB, arenaF, rowsF, arenaS, rowsS, depth, n_shards, state, nullptr);
-}
+__global__ void __launch_bounds__(256) k_minmax_scatter(FBK_GROUP_PARAMS, u64* state) { minmax_walk<false>(FBK_GROUP_ARGS, state, nullptr); }
 
-__global__ void __launch_bounds__(256) k_minmax_holders(const uint8_t* __restrict__ arenaA, const uint32_t* __restrict__ rowsA, uint32_t nA,
-                                                        const uint8_t* __restrict__ arenaB, const uint32_t* __restrict__ rowsB, uint32_t nB,
-                                                        const uint8_t* __restrict__ arenaF, const uint32_t* __restrict__ rowsF,
-                                                        const uint8_t* __restrict__ arenaS, const uint32_t* __restrict__ rowsS, uint32_t depth,
-                                                        uint32_t n_shards, u64* state, u64* __restrict__ counts) {
-  minmax_walk<true>(arenaA, rowsA, nA, arenaB, rowsB, nB, arenaF, rowsF, arenaS, rowsS, depth, n_shards, state, counts);
+__global__ void __launch_bounds__(256) k_minmax_holders(FBK_GROUP_PARAMS, u64* state, u64* __restrict__ counts) {
+  minmax_walk<true>(FBK_GROUP_ARGS, state, counts);
 }
 
 // out_cmin == nullptr: no counts

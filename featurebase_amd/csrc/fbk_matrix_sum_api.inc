@@ -10,45 +10,39 @@ namespace {
 constexpr uint64_t kMsumScratch = 1ull << 30;
 
 struct MsumPlan {
-  uint32_t n_a = 0, n_b = 0, n_shards = 0, depth = 0, n_chunks = 0, chunk = 0;
-  DenseOperands ops;
-  int A = 0, B = 0, F = 0, S = 0;  // its operands: A rows, B rows, the filter row, the BSI fragment
+  GroupFieldOperands gf;  // its operands, with n_a, n_b, depth, n_shards and the chunk
+  uint32_t n_chunks = 0;
   DevBuf chunks, dshard, result;
-  uint64_t width() const { return uint64_t(n_a) * n_b; }
+  uint64_t width() const { return uint64_t(gf.n_a) * gf.n_b; }
 };
 
 uint32_t msum_chunks_of(uint32_t depth) { return (depth + fbk::kMsumChunkBits - 1) / fbk::kMsumChunkBits; }
 
-int32_t msum_args_ok(const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b, const uint32_t* rows_b, uint32_t n_b,
-                     const fbk_batch* filter, const uint32_t* rows_f, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth,
-                     uint32_t n_shards) {
-  if (!bsi || (n_shards && !base_rows)) return fail(FBK_E_INVALID, "NULL argument");
-  if (!b && n_b != 1) return fail(FBK_E_INVALID, "count_matrix_sum: without B rows (the one-field GroupBy) n_b must be 1");
-  if (b) {
-    if (int32_t rc = count_matrix_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, n_shards)) return rc;
-  } else if (int32_t rc = count_matrix_args_ok(a, rows_a, n_a, a, rows_a, 1, filter, rows_f, n_shards)) {
+// The operand arguments of every GroupBy aggregate over an int field (g.a != nullptr is the caller's check).
+int32_t msum_args_ok(const GroupFieldArgs& g) {
+  if (!g.bsi || (g.n_shards && !g.base_rows)) return fail(FBK_E_INVALID, "NULL argument");
+  if (!g.b && g.n_b != 1) return fail(FBK_E_INVALID, "count_matrix_sum: without B rows (the one-field GroupBy) n_b must be 1");
+  if (g.b) {
+    if (int32_t rc = count_matrix_args_ok(g.a, g.rows_a, g.n_a, g.b, g.rows_b, g.n_b, g.filter, g.rows_f, g.n_shards)) return rc;
+  } else if (int32_t rc = count_matrix_args_ok(g.a, g.rows_a, g.n_a, g.a, g.rows_a, 1, g.filter, g.rows_f, g.n_shards)) {
     return rc;
   }
-  if (n_a > 4096 || n_b > 4096) return fail(FBK_E_INVALID, "count_matrix_sum: at most 4096 rows per side");
-  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
-  if (int32_t rc = check_rows(rows_a, uint64_t(n_shards) * n_a, a->n_rows, "count_matrix_sum A")) return rc;
-  if (b)
-    if (int32_t rc = check_rows(rows_b, uint64_t(n_shards) * n_b, b->n_rows, "count_matrix_sum B")) return rc;
-  if (filter)
-    if (int32_t rc = check_rows(rows_f, n_shards, filter->n_rows, "count_matrix_sum filter")) return rc;
-  return bsi_rows_ok(base_rows, n_shards, bit_depth, bsi->n_rows);
+  if (g.n_a > 4096 || g.n_b > 4096) return fail(FBK_E_INVALID, "count_matrix_sum: at most 4096 rows per side");
+  if (g.bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (int32_t rc = check_rows(g.rows_a, uint64_t(g.n_shards) * g.n_a, g.a->n_rows, "count_matrix_sum A")) return rc;
+  if (g.b)
+    if (int32_t rc = check_rows(g.rows_b, uint64_t(g.n_shards) * g.n_b, g.b->n_rows, "count_matrix_sum B")) return rc;
+  if (g.filter)
+    if (int32_t rc = check_rows(g.rows_f, g.n_shards, g.filter->n_rows, "count_matrix_sum filter")) return rc;
+  return bsi_rows_ok(g.base_rows, g.n_shards, g.bit_depth, g.bsi->n_rows);
 }
 
 // Validated arguments -> row lists on the device, scratch and result allocated: everything a run needs (n_shards > 0, width > 0).
-int32_t msum_prepare(fbk_ctx* ctx, MsumPlan& p, const fbk_batch* a, const uint32_t* rows_a, uint32_t n_a, const fbk_batch* b, const uint32_t* rows_b,
-                     uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth,
-                     uint32_t n_shards) {
-  p.n_a = n_a, p.n_b = n_b, p.n_shards = n_shards, p.depth = bit_depth, p.n_chunks = msum_chunks_of(bit_depth);
-  p.A = p.ops.add(a, rows_a, n_a), p.B = p.ops.add(b, rows_b, n_b), p.F = p.ops.add(filter, rows_f, 1);
-  p.S = p.ops.add(bsi, base_rows, bit_depth + 2, true);
-  p.chunk = even_chunk(n_shards, kMsumScratch, p.n_chunks * fbk::kMsumChunkBytes + kDenseRowBytes * p.ops.densified_rows() + 16 * p.width());
-  const uint32_t c = p.chunk;
-  if (int32_t rc = p.ops.upload(ctx, n_shards, c)) return rc;
+int32_t msum_prepare(fbk_ctx* ctx, MsumPlan& p, const GroupFieldArgs& g) {
+  p.n_chunks = msum_chunks_of(g.bit_depth);
+  p.gf.add(g, g.bit_depth);
+  const uint32_t c = even_chunk(g.n_shards, kMsumScratch, p.n_chunks * fbk::kMsumChunkBytes + kDenseRowBytes * p.gf.ops.densified_rows() + 16 * p.width());
+  if (int32_t rc = p.gf.upload(ctx, c)) return rc;
   if (p.n_chunks) HIP_TRY(p.chunks.alloc(ctx, uint64_t(c) * p.n_chunks * fbk::kMsumChunkBytes));
   HIP_TRY(p.dshard.alloc(ctx, uint64_t(c) * 2 * p.width() * 8));
   HIP_TRY(p.result.alloc(ctx, 2 * p.width() * 8));
@@ -57,17 +51,18 @@ int32_t msum_prepare(fbk_ctx* ctx, MsumPlan& p, const fbk_batch* a, const uint32
 
 // One execution, launch-only: p.result = {sums [n_a * n_b] (u64, wrapping), counts [n_a * n_b]}.
 int32_t msum_enqueue(fbk_ctx* ctx, MsumPlan& p) {
-  if (p.ops.layout_changed()) return fail(FBK_E_INVALID, "count_matrix_sum: a batch changed its layout since the query was prepared");
+  GroupFieldOperands& gf = p.gf;
+  if (gf.ops.layout_changed()) return fail(FBK_E_INVALID, "count_matrix_sum: a batch changed its layout since the query was prepared");
   const uint64_t width = p.width();
-  const uint32_t n_a = p.n_a, n_b = p.n_b;
+  const uint32_t n_a = gf.n_a, n_b = gf.n_b;
   HIP_TRY(hipMemsetAsync(p.result.p, 0, 2 * width * 8, ctx->stream));
   KernelSpan span(ctx);
-  for (uint32_t s0 = 0; s0 < p.n_shards; s0 += p.chunk) {
-    const uint32_t ns = std::min(p.chunk, p.n_shards - s0);
-    p.ops.densify(ctx, s0, ns);
-    const DenseView A = p.ops.view(p.A, s0), B = p.ops.view(p.B, s0), F = p.ops.view(p.F, s0), S = p.ops.view(p.S, s0);
+  for (uint32_t s0 = 0; s0 < gf.n_shards; s0 += gf.chunk) {
+    const uint32_t ns = std::min(gf.chunk, gf.n_shards - s0);
+    gf.ops.densify(ctx, s0, ns);
+    const auto [A, B, F, S] = gf.views(s0);
     if (p.n_chunks)
-      hipLaunchKernelGGL(fbk::k_msum_chunks, dim3(ns * 128u), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, p.depth, p.n_chunks, p.chunks.as<uint8_t>());
+      hipLaunchKernelGGL(fbk::k_msum_chunks, dim3(ns * 128u), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, gf.depth, p.n_chunks, p.chunks.as<uint8_t>());
     HIP_TRY(hipMemsetAsync(p.dshard.p, 0, uint64_t(ns) * 2 * width * 8, ctx->stream));
     namespace mp = fbk_count_matrix_plan;  // slots per block: whole shards while the grid still holds ~2048 blocks
     const uint32_t tiles = mp::tiles32(n_a, n_b);
@@ -120,15 +115,16 @@ int32_t fbk_count_matrix_sum(fbk_ctx* ctx, const fbk_batch* a, const uint32_t* r
                              uint32_t bit_depth, uint32_t n_shards, int64_t* out_sums, uint64_t* out_counts) try {
   FBK_ENTER(ctx);
   if (!ctx || !a || !out_sums || !out_counts) return fail(FBK_E_INVALID, "NULL argument");
-  if (int32_t rc = msum_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
-  const uint64_t width = uint64_t(n_a) * n_b;
+  const GroupFieldArgs args{a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards};
+  if (int32_t rc = msum_args_ok(args)) return rc;
+  const uint64_t width = args.width();
   std::memset(out_sums, 0, width * 8);
   std::memset(out_counts, 0, width * 8);
   if (n_shards == 0 || width == 0) return FBK_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
   MsumPlan p;
-  if (int32_t rc = msum_prepare(ctx, p, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
+  if (int32_t rc = msum_prepare(ctx, p, args)) return rc;
   if (int32_t rc = msum_enqueue(ctx, p)) return rc;
   return msum_read(ctx, p, out_sums, out_counts);
 } FBK_ABI_CATCH(ctx)

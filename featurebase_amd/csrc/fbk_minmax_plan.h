@@ -4,12 +4,14 @@
 //   kMinmaxDescentCells     the most groups FBK_MINMAX_AUTO gives to the descent; above it the per-column scatter runs;
 //   path()                  the path of a call from its shape and its flags (0: the flags / shape are an error);
 //   descent_grid()          the unit blocks of a descent launch: bounds the partials;
-//   densify_chunk()         the shards per pass when an operand goes through DenseOperands.
+//   densify_chunk()         the shards per pass when an operand goes through DenseOperands (fbk_dense_policy.h's even_chunk).
 // The tests read both constants through the checker: they build a case exactly at each boundary.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
+
+#include "fbk_dense_policy.h"
 
 namespace fbk_minmax_plan {
 
@@ -46,13 +48,8 @@ inline uint32_t descent_grid(uint32_t n_shards, uint64_t cells) {
 }
 
 // Shards per pass: at most 2^30 / (2^17 * R) of them (R = the rows densified per shard), dealt evenly over the fewest passes
-// (fbk_dense_operands.inc's even_chunk: fbk_count_matrix_distinct's stage 2 arithmetic).
-constexpr uint64_t kScratch = 1ull << 30, kRowBytes = 1ull << 17;
-inline uint32_t densify_chunk(uint32_t n_shards, uint64_t densified) {
-  if (n_shards == 0 || densified == 0) return n_shards;
-  const uint64_t most = std::max<uint64_t>(1, std::min<uint64_t>(n_shards, kScratch / (kRowBytes * densified)));
-  const uint64_t passes = (n_shards + most - 1) / most;
-  return uint32_t((n_shards + passes - 1) / passes);
-}
+// (fbk_count_matrix_distinct's stage 2 arithmetic).
+constexpr uint64_t kScratch = 1ull << 30;
+inline uint32_t densify_chunk(uint32_t n_shards, uint64_t densified) { return fbk::even_chunk(n_shards, kScratch, fbk::kDenseRowBytes * densified); }
 
 }  // namespace fbk_minmax_plan

@@ -44,11 +44,10 @@ int32_t fbk_bsi_moments(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* base_r
 
   DenseOperands ops;
   const int kX = ops.add(x, base_rows_x, depth_x + 2, true), kY = ops.add(y, base_rows_y, depth_y + 2, true), kF = ops.add(filter, rows_f, 1);
-  // (the plan header restates DenseOperands' count and even_chunk so that the stand-alone check covers them: they must agree)
+  // (the plan header restates DenseOperands' count so that the stand-alone check covers it: they must agree)
   const uint64_t densified = mp::densified_rows(!x->dense, depth_x, y != nullptr, y && !y->dense, depth_y, filter != nullptr, filter && !filter->dense);
   const uint32_t chunk = mp::densify_chunk(n_shards, densified);
-  if (densified != ops.densified_rows() || chunk != even_chunk(n_shards, mp::kScratch, kDenseRowBytes * ops.densified_rows()))
-    return fail(FBK_E_HIP, "bsi_moments: fbk_moments_plan.h and fbk_dense_operands.inc disagree on the densify chunk");
+  if (densified != ops.densified_rows()) return fail(FBK_E_HIP, "bsi_moments: fbk_moments_plan.h and fbk_dense_operands.inc disagree on the densified rows");
   if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
   // one partial matrix per block, as many blocks per CU as are resident (kMomBlocksPerCU): the blocks walk their units of 16 stripes round robin.  pack: the column
   // blocks that share the tile (a stripe is pack * 1024 columns)

@@ -5,12 +5,14 @@
 //   rows()               the row of the byte matrix M each chunk and the 0/1 mask take (G = M · Mᵀ is at most 21 x 21 of 32 x 32);
 //   packing()            how many column blocks share the 32-row tile when the call has few rows;
 //   kMaxColumnsPerI32    how many columns an i32 accumulator may cover before it is flushed into an i64;
-//   densify_chunk()      the shards per pass when an operand goes through DenseOperands;
+//   densify_chunk()      the shards per pass when an operand goes through DenseOperands (fbk_dense_policy.h's even_chunk);
 //   fold()               the i64 chunk-pair matrix -> n and the five sums, modulo 2^128.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
+
+#include "fbk_dense_policy.h"
 
 namespace fbk_moments_plan {
 
@@ -49,14 +51,9 @@ static_assert((1ull << 17) <= kMaxColumnsPerI32 && (1ull << 18) > kMaxColumnsPer
 inline uint64_t densified_rows(bool x_encoded, uint32_t depth_x, bool has_y, bool y_encoded, uint32_t depth_y, bool has_f, bool f_encoded) {
   return (x_encoded ? depth_x + 2 : 0) + (has_y && y_encoded ? depth_y + 2 : 0) + (has_f && f_encoded ? 1 : 0);
 }
-// Shards per pass: at most 2^30 / (2^17 * R) of them, dealt evenly over the fewest passes (fbk_dense_operands.inc's even_chunk).
-constexpr uint64_t kScratch = 1ull << 30, kRowBytes = 1ull << 17;
-inline uint32_t densify_chunk(uint32_t n_shards, uint64_t densified) {
-  if (n_shards == 0 || densified == 0) return n_shards;
-  const uint64_t most = std::max<uint64_t>(1, std::min<uint64_t>(n_shards, kScratch / (kRowBytes * densified)));
-  const uint64_t passes = (n_shards + most - 1) / most;
-  return uint32_t((n_shards + passes - 1) / passes);
-}
+// Shards per pass: at most 2^30 / (2^17 * R) of them, dealt evenly over the fewest passes.
+constexpr uint64_t kScratch = 1ull << 30;
+inline uint32_t densify_chunk(uint32_t n_shards, uint64_t densified) { return fbk::even_chunk(n_shards, kScratch, fbk::kDenseRowBytes * densified); }
 
 // n and the five sums modulo 2^128 (two's complement)
 struct Sums {

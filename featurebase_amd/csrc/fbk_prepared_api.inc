@@ -123,7 +123,8 @@ int32_t fbk_query_count_matrix_sum(fbk_ctx* ctx, const fbk_batch* a, const uint3
   FBK_ENTER(ctx);
   if (!ctx || !a || !out_query) return fail(FBK_E_INVALID, "NULL argument");
   *out_query = nullptr;
-  if (int32_t rc = msum_args_ok(a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards)) return rc;
+  const GroupFieldArgs args{a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards};
+  if (int32_t rc = msum_args_ok(args)) return rc;
   if (n_shards == 0 || n_a == 0 || n_b == 0) return fail(FBK_E_INVALID, "query: empty count matrix");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
@@ -131,7 +132,7 @@ int32_t fbk_query_count_matrix_sum(fbk_ctx* ctx, const fbk_batch* a, const uint3
   if (!q.q) return fail(FBK_E_NOMEM, "host allocation failed");
   q->result_bytes = uint64_t(n_a) * n_b * 16;  // (in the plan's own buffer)
   q->msum.reset(new MsumPlan());
-  return q.finish(msum_prepare(ctx, *q->msum, a, rows_a, n_a, b, rows_b, n_b, filter, rows_f, bsi, base_rows, bit_depth, n_shards), out_query);
+  return q.finish(msum_prepare(ctx, *q->msum, args), out_query);
 } FBK_ABI_CATCH(ctx)
 
 int32_t fbk_query_fold_intersection_count(fbk_ctx* ctx, int32_t op, const fbk_batch* batch, const uint32_t* rows, uint64_t n_groups, uint32_t k,
