@@ -507,9 +507,7 @@ static int32_t bsi_distinct_device(fbk_ctx* ctx, const fbk_batch* batch, const u
   if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
   // Where a cell's values go is known before the transpose runs (k_bsi_cell_scan): without a filter the stored cardinalities of the
   // exists row are the counts, with one a count pass over exists ∩ filter comes first.
-  for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-    const uint32_t ns = std::min(chunk, n_shards - s0);
-    ops.densify(ctx, s0, ns);
+  ops.for_each_chunk(ctx, true, DenseOperands::Densify::together, [&](uint32_t s0, uint32_t ns) {
     const DenseView S = ops.view(kS, s0), F = ops.view(kF, s0);
     u64* cb = dbase.as<u64>() + uint64_t(s0) * fbk::kSlots;  // (the chunk's last entry is the next chunk's first: the same number)
     if (filter)
@@ -519,7 +517,7 @@ static int32_t bsi_distinct_device(fbk_ctx* ctx, const fbk_batch* batch, const u
                        filter ? dcounts.as<uint32_t>() : (const uint32_t*)nullptr, ns * fbk::kSlots, cb, dcur.as<u64>());
     hipLaunchKernelGGL(fbk::k_bsi_values, dim3(ns * fbk::kSlots * bsi_values_split(ns)), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, bit_depth, F.arena, F.rows,
                        dvals.as<long long>(), u64(upper), cb, d_flag, bsi_values_split(ns));
-  }
+  });
   HIP_TRY(hipGetLastError());
   u64 h_cur[3] = {0, 0, 0};
   HIP_TRY(hipMemcpyAsync(h_cur, dcur.p, 24, hipMemcpyDeviceToHost, ctx->stream));

@@ -11,7 +11,7 @@ constexpr uint64_t kCubeScratch = 1ull << 30;
 constexpr uint64_t kCubeMaxCells = 1ull << 24;
 
 struct CubePlan {
-  uint32_t n_p = 0, n_a = 0, n_b = 0, n_shards = 0, chunk = 0;
+  uint32_t n_p = 0, n_a = 0, n_b = 0;
   DenseOperands ops;
   int P = 0, A = 0, B = 0, F = 0;  // its operands: the rows of the three fields, the filter row
   DevBuf dshard, result;
@@ -36,11 +36,11 @@ int32_t cube_args_ok(const fbk_batch* p, const uint32_t* rows_p, uint32_t n_p, c
 int32_t cube_prepare(fbk_ctx* ctx, CubePlan& c, const fbk_batch* p, const uint32_t* rows_p, uint32_t n_p, const fbk_batch* a, const uint32_t* rows_a,
                      uint32_t n_a, const fbk_batch* b, const uint32_t* rows_b, uint32_t n_b, const fbk_batch* filter, const uint32_t* rows_f,
                      uint32_t n_shards) {
-  c.n_p = n_p, c.n_a = n_a, c.n_b = n_b, c.n_shards = n_shards;
+  c.n_p = n_p, c.n_a = n_a, c.n_b = n_b;
   c.P = c.ops.add(p, rows_p, n_p), c.A = c.ops.add(a, rows_a, n_a), c.B = c.ops.add(b, rows_b, n_b), c.F = c.ops.add(filter, rows_f, 1);
-  c.chunk = even_chunk(n_shards, kCubeScratch, kDenseRowBytes * c.ops.densified_rows() + 8 * c.cells());
-  if (int32_t rc = c.ops.upload(ctx, n_shards, c.chunk)) return rc;
-  HIP_TRY(c.dshard.alloc(ctx, uint64_t(c.chunk) * c.cells() * 8));
+  const uint32_t chunk = even_chunk(n_shards, kCubeScratch, kDenseRowBytes * c.ops.densified_rows() + 8 * c.cells());
+  if (int32_t rc = c.ops.upload(ctx, n_shards, chunk)) return rc;
+  HIP_TRY(c.dshard.alloc(ctx, uint64_t(chunk) * c.cells() * 8));
   HIP_TRY(c.result.alloc(ctx, c.cells() * 8));
   return FBK_OK;
 }
@@ -55,9 +55,7 @@ int32_t cube_enqueue(fbk_ctx* ctx, CubePlan& c) {
   namespace mp = fbk_count_matrix_plan;  // P rows per block, tiles, slots per block
   const uint32_t pt = mp::cube_pt(n_p);
   const uint64_t tiles = mp::cube_tiles(n_p, n_a, n_b);
-  for (uint32_t s0 = 0; s0 < c.n_shards; s0 += c.chunk) {
-    const uint32_t ns = std::min(c.chunk, c.n_shards - s0);
-    c.ops.densify(ctx, s0, ns);
+  if (int32_t rc = c.ops.for_each_chunk(ctx, true, DenseOperands::Densify::together, [&](uint32_t s0, uint32_t ns) -> int32_t {
     const DenseView P = c.ops.view(c.P, s0), A = c.ops.view(c.A, s0), B = c.ops.view(c.B, s0), F = c.ops.view(c.F, s0);
     HIP_TRY(hipMemsetAsync(c.dshard.p, 0, uint64_t(ns) * cells * 8, ctx->stream));
     const uint32_t spb = mp::slots_per_block(tiles, ns, mp::kCubeFloor, mp::kCubeEnough, uint32_t(ctx->opt.matrix_spb));  // tests walk every value
@@ -81,7 +79,8 @@ int32_t cube_enqueue(fbk_ctx* ctx, CubePlan& c) {
     }
     hipLaunchKernelGGL(fbk::k_reduce_shards, dim3(uint32_t((cells + 255) / 256), std::min<uint32_t>(ns, 64)), dim3(256), 0, ctx->stream, c.dshard.as<u64>(), ns,
                        cells, c.result.as<u64>());
-  }
+    return FBK_OK;
+  })) return rc;
   HIP_TRY(hipGetLastError());
   return FBK_OK;
 }

@@ -6,8 +6,8 @@
 // (k_densify_rows) into scratch, and the kernel reads the scratch through a list of the rows' places in it.  DenseOperands decides
 // which, builds the lists, lays the operands of a call out in ONE scratch buffer in the order they were added, and hands a call
 // site the (arena, rows) pair its kernel takes for the chunk [s0, s0 + ns).  How many shards a chunk holds is the caller's own
-// arithmetic (fbk_dense_policy.h's even_chunk with its budget and per-shard term: fbk.h documents it per call).  The GroupBy
-// aggregates over an int field share one frame on top of it (fbk_group_field.inc).
+// arithmetic (fbk_dense_policy.h's even_chunk with its budget and per-shard term: fbk.h documents it per call); the loop over the
+// chunks is for_each_chunk.  Two frames stand on it: GroupFieldOperands (fbk_group_field.inc), FieldOperands (fbk_sort_api.inc).
 
 namespace {
 
@@ -89,6 +89,25 @@ class DenseOperands {
       o.h_rows = nullptr;  // (the caller's list: not kept beyond the call)
     }
     if (at) HIP_TRY(scratch_.alloc(ctx, at * kDenseRowBytes));
+    n_shards_ = n_shards, chunk_ = chunk;
+    return FBK_OK;
+  }
+
+  // THE walk over the shards upload() laid out: for every chunk [s0, s0 + ns), densify, then fn(s0, ns).  fn returns nothing, or an
+  // error code that ends the walk and is returned.  A call that walks more than once says which walk is its first: a single chunk
+  // is still in the scratch for the later ones and is not densified again.
+  enum class Densify { together, each };  // one launch for all operands, or one per operand in the order they were added
+  template <class Fn>
+  int32_t for_each_chunk(fbk_ctx* ctx, bool first_walk, Densify how, Fn&& fn) {
+    const bool stale = first_walk || chunk_ < n_shards_;
+    for (uint32_t s0 = 0; s0 < n_shards_; s0 += chunk_) {
+      const uint32_t ns = std::min(chunk_, n_shards_ - s0);
+      if (stale && how == Densify::together) densify(ctx, s0, ns);
+      else if (stale)
+        for (size_t k = 0; k < ops_.size(); ++k) densify_one(ctx, int(k), s0, ns);
+      if constexpr (std::is_void_v<decltype(fn(s0, ns))>) fn(s0, ns);
+      else if (int32_t rc = fn(s0, ns)) return rc;
+    }
     return FBK_OK;
   }
 
@@ -139,6 +158,7 @@ class DenseOperands {
     return {o.batch->d_slots, o.batch->d_arena, o.d_src + uint64_t(s0) * o.rps + i0, uint64_t(ns) * nr, static_cast<uint8_t*>(scratch_.p) + o.at * kDenseRowBytes};
   }
   std::vector<Op> ops_;
+  uint32_t n_shards_ = 0, chunk_ = 0;  // upload()'s
   DevBuf lists_;
   DevBuf scratch_;
 };

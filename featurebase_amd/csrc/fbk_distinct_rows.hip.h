@@ -50,7 +50,7 @@ __global__ void __launch_bounds__(256) k_drow_presence(const uint8_t* __restrict
   const int lane = threadIdx.x & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const TrConst tc = tr_const(lane);
-  const SortKey sk{0, 0, 0, 1};
+  const SortKey sk = value_key();
   const uint64_t units = (uint64_t)ns * kExtractUnits;
   for (uint64_t u = (uint64_t)blockIdx.x * 4 + wv; u < units; u += (uint64_t)gridDim.x * 4) {
     const uint32_t ls = uint32_t(u / kExtractUnits), un = uint32_t(u % kExtractUnits);
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(256) k_drow_inner(const uint8_t* __restrict__ 
   const int lane = threadIdx.x & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const TrConst tc = tr_const(lane);
-  const SortKey sk{0, 0, 0, 1};
+  const SortKey sk = value_key();
   const uint64_t units = (uint64_t)ns * kExtractUnits;
   for (uint64_t u = (uint64_t)blockIdx.x * 4 + wv; u < units; u += (uint64_t)gridDim.x * 4) {
     const uint32_t ls = uint32_t(u / kExtractUnits), un = uint32_t(u % kExtractUnits);
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(256) k_drow_scatter(const uint8_t* __restrict_
   const int lane = threadIdx.x & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const TrConst tc = tr_const(lane);
-  const SortKey sk{0, 0, 0, 1};
+  const SortKey sk = value_key();
   const uint64_t units = (uint64_t)ns * kExtractUnits;
   for (uint64_t u = (uint64_t)blockIdx.x * 4 + wv; u < units; u += (uint64_t)gridDim.x * 4) {
     const uint32_t ls = uint32_t(u / kExtractUnits), un = uint32_t(u % kExtractUnits);

@@ -1,9 +1,9 @@
 // fbk_distinct_rows_api.inc — fbk_bsi_distinct_rows (Distinct() over an int field as a device Row, the operand of a join):
 // fbk_distinct_rows.hip.h.  Included by fbk.hip after fbk_quantile_api.inc.
 //
-// Two walks over the shards (presence, scatter), each densifying what is not dense a chunk of shards at a time exactly as
-// fbk_bsi_sort's.  Device scratch beyond the output arena (fbk.h documents it): the densify chunk (<= 2^28), two presence bitmaps
-// of <= 2^20 bytes, their word prefixes (half of that), the run counts and cardinalities of the output cells, the row lists.
+// Two walks over the shards (presence, scatter) of fbk_bsi_sort's FieldOperands (fbk_sort_api.inc).  Device scratch beyond the
+// output arena (fbk.h documents it): the densify chunk (<= 2^28), two presence bitmaps of <= 2^20 bytes, their word prefixes (half
+// of that), the run counts and cardinalities of the output cells, the row lists.
 
 namespace {
 
@@ -29,27 +29,13 @@ int32_t fbk_bsi_distinct_rows(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t
   if (bit_depth > 63)
     return fail(FBK_E_INVALID, "distinct rows: bit depth > 63 (a magnitude of 2^63 and more has no position in a row); fbk_bsi_distinct returns such a field's values");
   if (flags & ~uint32_t(FBK_SETOP_OPTIMIZE)) return fail(FBK_E_INVALID, "distinct rows: unknown flags");
-  if (n_shards > (1u << 20)) return fail(FBK_E_INVALID, "distinct rows: at most 2^20 shards per call");
-  if (!ctx || !bsi || (n_shards && !base_rows) || (filter && n_shards && !rows_f)) return fail(FBK_E_INVALID, "NULL argument");
-  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, bsi->n_rows)) return rc;
-  if (filter)
-    if (int32_t rc = check_rows(rows_f, n_shards, filter->n_rows, "distinct rows filter")) return rc;
+  if (int32_t rc = field_args_ok(ctx, bsi, base_rows, bit_depth, filter, rows_f, n_shards, 1u << 20, "distinct rows: at most 2^20 shards per call", "distinct rows filter")) return rc;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
 
-  // the operands and the walk over the shards: launch(S, F, ns, grid) per chunk, everything of the chunk dense
-  DenseOperands ops;
-  const int kF = ops.add(filter, rows_f, 1), kS = ops.add(bsi, base_rows, bit_depth + 2, true);
-  const uint32_t chunk = n_shards ? even_chunk(n_shards, kExtractScratch, kDenseRowBytes * ops.densified_rows()) : 1;
+  FieldOperands fo;  // (n_shards == 0: never uploaded, never walked)
+  fo.add(bsi, base_rows, bit_depth, filter, rows_f, n_shards);
   DevBuf pres, pre, inner;
-  auto walk = [&](auto&& launch) {
-    for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-      const uint32_t ns = std::min(chunk, n_shards - s0);
-      ops.densify_one(ctx, kF, s0, ns);  // (a launch each: the filter's rows, then the field's)
-      ops.densify_one(ctx, kS, s0, ns);
-      launch(ops.view(kS, s0), ops.view(kF, s0), ns, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)));
-    }
-  };
 
   // 1. the window of shards per sign: by arithmetic where 2^bit_depth + |base| bounds it, else from the minimum and the maximum
   fbk::DrowWindow win{};
@@ -82,11 +68,11 @@ int32_t fbk_bsi_distinct_rows(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t
       bool ok_neg = vmin >= 0 || drow_window(in[1], 0 - uint64_t(vmin), &win.lo[1], &win.span[1]);
       if ((!ok_pos || !ok_neg) && vmin < 0 && vmax >= 0) {
         // ... unless that is too wide a guess: one walk finds the smallest position of either sign
-        if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
+        if (int32_t rc = fo.upload(ctx)) return rc;
         uploaded = true;
         HIP_TRY(inner.alloc(ctx, 16));
         HIP_TRY(hipMemsetAsync(inner.p, 0xFF, 16, ctx->stream));
-        walk([&](const DenseView& S, const DenseView& F, uint32_t ns, dim3 grid) {
+        fo.for_each_chunk(ctx, [&](const DenseView& S, const DenseView& F, uint32_t, uint32_t ns, dim3 grid) {
           hipLaunchKernelGGL(fbk::k_drow_inner, grid, dim3(256), 0, ctx->stream, S.arena, S.rows, F.arena, F.rows, ns, bit_depth, u64(base), inner.as<u64>());
         });
         HIP_TRY(hipGetLastError());
@@ -109,10 +95,10 @@ int32_t fbk_bsi_distinct_rows(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t
   std::vector<uint64_t> hp(n_words);
   if (n_words) {
     if (!uploaded)
-      if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
+      if (int32_t rc = fo.upload(ctx)) return rc;
     HIP_TRY(pres.alloc(ctx, uint64_t(n_words) * 8));
     HIP_TRY(hipMemsetAsync(pres.p, 0, uint64_t(n_words) * 8, ctx->stream));
-    walk([&](const DenseView& S, const DenseView& F, uint32_t ns, dim3 grid) {
+    fo.for_each_chunk(ctx, [&](const DenseView& S, const DenseView& F, uint32_t, uint32_t ns, dim3 grid) {
       hipLaunchKernelGGL(fbk::k_drow_presence, grid, dim3(256), 0, ctx->stream, S.arena, S.rows, F.arena, F.rows, ns, bit_depth, u64(base), win, pres.as<u64>());
     });
     HIP_TRY(hipGetLastError());
@@ -153,7 +139,7 @@ int32_t fbk_bsi_distinct_rows(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t
   if (n) {
     HIP_TRY(pre.alloc(ctx, uint64_t(n_words) * 4));
     HIP_TRY(hipMemcpyAsync(pre.p, hpre.data(), uint64_t(n_words) * 4, hipMemcpyHostToDevice, ctx->stream));
-    walk([&](const DenseView& S, const DenseView& F, uint32_t ns, dim3 grid) {
+    fo.for_each_chunk(ctx, [&](const DenseView& S, const DenseView& F, uint32_t, uint32_t ns, dim3 grid) {
       hipLaunchKernelGGL(fbk::k_drow_scatter, grid, dim3(256), 0, ctx->stream, S.arena, S.rows, F.arena, F.rows, ns, bit_depth, u64(base), win,
                          pres.as<u64>(), pre.as<uint32_t>(), uint32_t(n_sign[0]), uint32_t(n), reinterpret_cast<u64*>(o->d_arena));
     });

@@ -13,7 +13,7 @@
 
 namespace {
 
-constexpr uint64_t kExtractScratch = 1ull << 28;
+using fbk_select_plan::kExtractScratch, fbk_select_plan::densify_chunk;  // shared with Sort, the quantiles and Distinct rows
 
 uint32_t extract_grid(uint64_t units) { return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((units + 3) / 4, 8192))); }
 
@@ -58,7 +58,7 @@ int32_t fbk_extract_open(fbk_ctx* ctx, const fbk_batch* filter, const uint32_t* 
   if (int32_t rc = set_device(ctx)) return rc;
   DenseOperands ops;
   const int kF = ops.add(filter, rows_f, 1);
-  const uint32_t chunk = even_chunk(n_shards, kExtractScratch, kDenseRowBytes * ops.densified_rows());
+  const uint32_t chunk = densify_chunk(n_shards, ops.densified_rows());
   DevBuf unit_pre, shard_tot, shard_base, carry;
   if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
   HIP_TRY(h->ids.alloc(ctx, uint64_t(n_shards) * 8));
@@ -76,13 +76,11 @@ int32_t fbk_extract_open(fbk_ctx* ctx, const fbk_batch* filter, const uint32_t* 
   HIP_TRY(carry.alloc(ctx, 8));
   HIP_TRY(hipMemsetAsync(carry.p, 0, 8, ctx->stream));
   // the filter's columns per unit and per shard, from its words
-  for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-    const uint32_t ns = std::min(chunk, n_shards - s0);
-    ops.densify(ctx, s0, ns);
+  ops.for_each_chunk(ctx, true, DenseOperands::Densify::together, [&](uint32_t s0, uint32_t ns) {
     const DenseView F = ops.view(kF, s0);
     hipLaunchKernelGGL(fbk::k_extract_scan, dim3(ns), dim3(1024), 0, ctx->stream, F.arena, F.rows, unit_pre.as<uint32_t>() + uint64_t(s0) * fbk::kExtractUnits,
                        shard_tot.as<uint32_t>() + s0);
-  }
+  });
   exclusive_scan_u32(ctx, shard_tot.as<uint32_t>(), n_shards, shard_base.as<u64>(), carry.as<u64>());
   HIP_TRY(hipGetLastError());
   std::vector<uint64_t> base(uint64_t(n_shards) + 1);
@@ -107,7 +105,7 @@ int32_t fbk_extract_open(fbk_ctx* ctx, const fbk_batch* filter, const uint32_t* 
   const uint64_t su_end = uint64_t(span) * fbk::kExtractUnits;
   HIP_TRY(h->sel.alloc(ctx, su_end * fbk::kExtractWords * 8));
   HIP_TRY(h->upre.alloc(ctx, (su_end + 1) * 4));
-  for (uint32_t s0 = 0; s0 < span; s0 += chunk) {  // (the chunk of the first pass: its scratch and lists)
+  for (uint32_t s0 = 0; s0 < span; s0 += chunk) {  // (not for_each_chunk: a sub-span, walked with the first pass's chunk, scratch and lists)
     const uint32_t ns = std::min(chunk, span - s0);
     ops.densify(ctx, s_first + s0, ns);
     const DenseView F = ops.view(kF, s_first + s0);
@@ -160,18 +158,16 @@ int32_t fbk_extract_bsi(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* bsi, cons
   const uint32_t span = h->span;
   DenseOperands ops;
   const int kS = ops.add(bsi, base_rows + h->s_first, bit_depth + 2, true);
-  const uint32_t chunk = even_chunk(span, kExtractScratch, kDenseRowBytes * ops.densified_rows());
+  const uint32_t chunk = densify_chunk(span, ops.densified_rows());
   DevBuf vals, pres;
   if (int32_t rc = ops.upload(ctx, span, chunk)) return rc;
   HIP_TRY(vals.alloc(ctx, h->n * 8));
   HIP_TRY(pres.alloc(ctx, h->n));
-  for (uint32_t s0 = 0; s0 < span; s0 += chunk) {
-    const uint32_t ns = std::min(chunk, span - s0);
-    ops.densify(ctx, s0, ns);
+  ops.for_each_chunk(ctx, true, DenseOperands::Densify::together, [&](uint32_t s0, uint32_t ns) {
     const DenseView S = ops.view(kS, s0);
     hipLaunchKernelGGL(fbk::k_extract_bsi, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, s0, bit_depth,
                        h->sel.as<u64>(), h->upre.as<uint32_t>(), u64(h->n), vals.as<long long>(), pres.as<uint8_t>());
-  }
+  });
   HIP_TRY(hipGetLastError());
   D2H back(ctx);
   HIP_TRY(back.add(out_values, vals.p, h->n * 8));
@@ -212,7 +208,7 @@ int32_t fbk_extract_rows(fbk_ctx* ctx, fbk_extract* h, const fbk_batch* a, const
   HIP_TRY(offs.alloc(ctx, (n + 1) * 8));
   // one walk over the span, a chunk of shards and a block of rows per launch: counts (fill == false), then the items
   auto walk = [&](bool fill, u64 m) {
-    for (uint32_t s0 = 0; s0 < span; s0 += chunk) {
+    for (uint32_t s0 = 0; s0 < span; s0 += chunk) {  // (not for_each_chunk: a block of rows is densified inside the chunk)
       const uint32_t ns = std::min(chunk, span - s0);
       for (uint32_t i0 = 0; i0 < n_a; i0 += block) {
         const uint32_t nr = std::min(block, n_a - i0);

@@ -26,7 +26,7 @@ struct GroupFieldViews {  // what the kernels take for one chunk
 struct GroupFieldOperands {
   DenseOperands ops;
   int A = 0, B = 0, F = 0, S = 0;  // the operands' numbers in ops
-  uint32_t n_a = 0, n_b = 0, depth = 0, n_shards = 0, chunk = 0;
+  uint32_t n_a = 0, n_b = 0, depth = 0, n_shards = 0;
 
   // depth: the planes the kernels read (the fragment's exists and sign rows come with them).  The chunk is the caller's rule over
   // ops.densified_rows(), so it is taken between add() and upload().
@@ -35,22 +35,14 @@ struct GroupFieldOperands {
     A = ops.add(g.a, g.rows_a, g.n_a), B = ops.add(g.b, g.rows_b, g.n_b), F = ops.add(g.filter, g.rows_f, 1);
     S = ops.add(g.bsi, g.base_rows, depth_read + 2, true);
   }
-  int32_t upload(fbk_ctx* ctx, uint32_t chunk_shards) {
-    chunk = chunk_shards;
-    return ops.upload(ctx, n_shards, chunk);
-  }
+  int32_t upload(fbk_ctx* ctx, uint32_t chunk) { return ops.upload(ctx, n_shards, chunk); }
 
   GroupFieldViews views(uint32_t s0) const { return {ops.view(A, s0), ops.view(B, s0), ops.view(F, s0), ops.view(S, s0)}; }
 
-  // fn(views, s0, ns) for every chunk [s0, s0 + ns) of the shards, densified.  A call that walks the operands more than once says
-  // which walk is its first: a single chunk is still in the scratch for the later ones and is not densified again.
+  // fn(views, s0, ns) for every chunk [s0, s0 + ns) of the shards, densified in one launch (DenseOperands::for_each_chunk)
   template <class Fn>
   void for_each_chunk(fbk_ctx* ctx, bool first_walk, Fn fn) {
-    for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-      const uint32_t ns = std::min(chunk, n_shards - s0);
-      if (first_walk || chunk < n_shards) ops.densify(ctx, s0, ns);
-      fn(views(s0), s0, ns);
-    }
+    ops.for_each_chunk(ctx, first_walk, DenseOperands::Densify::together, [&](uint32_t s0, uint32_t ns) { fn(views(s0), s0, ns); });
   }
 
   // blocks of a group_column_walk launch (fbk_group_walk.hip.h) over ns shards: four units of kGroupWalkWords words a block

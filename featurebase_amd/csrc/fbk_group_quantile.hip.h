@@ -34,13 +34,6 @@ struct GquantSlot {  // a request of a group on its way down the digits
   u64 rank;          // its rank among the group's columns with that prefix
 };
 
-// fbk_sort.hip.h's key as fbk_bsi_quantiles takes it (ascending, stored zeros take part), from the depth: built in the kernel, where
-// its constant fields cost no scalar registers
-__device__ __forceinline__ SortKey gquant_key(uint32_t depth) {
-  const bool wide = depth >= 63;
-  return SortKey{wide ? 1ull << 63 : 0ull, wide ? 0ull : 1ull << depth, 0ull, 1u};
-}
-
 __device__ __forceinline__ void gquant_add(u64* p) { atomicAdd(reinterpret_cast<unsigned long long*>(p), 1ull); }
 __device__ __forceinline__ void gquant_add(uint32_t* p) { atomicAdd(p, 1u); }
 
@@ -49,7 +42,7 @@ __device__ __forceinline__ void gquant_add(uint32_t* p) { atomicAdd(p, 1u); }
 template <class Counter>
 __device__ __forceinline__ void gquant_walk(FBK_GROUP_PARAMS, uint32_t shift, uint32_t wbits, uint32_t dbits, uint32_t n_h,
                                             const GquantSlot* __restrict__ slots, Counter* hist) {
-  const SortKey sk = gquant_key(depth);
+  const SortKey sk = select_key(depth, false, true);  // as fbk_bsi_quantiles'; built here, where its constant fields cost no scalar registers
   const int lane = threadIdx.x & 63;
   const uint32_t bins = 1u << dbits, pshift = n_h ? shift + wbits : 0;  // (n_h != 0: shift + wbits < 64); the digit: wbits <= dbits bits
   uint32_t digit = 0;  // of the lane's column's key
@@ -138,7 +131,7 @@ __global__ void __launch_bounds__(256) k_gquant_resolve(const u64* __restrict__ 
   while (before + c <= rank && b + 1 < (lane + 1) * per) before += c, c = h[++b];
   prefix = (prefix << wbits) | b, rank -= before;
   slots[pair] = {prefix, rank};
-  if (last) out_values[pair] = sort_value(prefix, gquant_key(depth)), out_counts[pair] = c;
+  if (last) out_values[pair] = sort_value(prefix, select_key(depth, false, true)), out_counts[pair] = c;
 }
 
 }  // namespace fbk

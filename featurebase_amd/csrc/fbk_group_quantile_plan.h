@@ -1,7 +1,7 @@
 // fbk_group_quantile_plan.h — host rules of fbk_count_matrix_quantiles (HIP-free: compiled into the library and into the stand-alone
 // check of the tests, tests/cpp/gquant_plan_check.cpp).  What fbk_group_quantile_api.inc decides before it launches, written once:
 //   kLdsDigitBits / kGlobalDigitBits  the radix digit of each kernel path (fbk_group_quantile.hip.h);
-//   key_bits(), passes()              the bits of the key (fbk_sort.hip.h's SortKey) and the passes over the planes;
+//   key_bits(), passes()              the bits of the key (fbk_select_plan.h's SortKey) and the passes over the planes;
 //   lds_pairs_cap()                   the most histograms (groups x max(1, n_q)) the LDS path keeps in a block's 64 KiB;
 //   scratch_bytes(), kScratchBound    the histograms in device memory and the most a call may ask for;
 //   path()                            the path of a call from its shape and its flags (0: the flags / shape are an error);
@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "fbk_dense_policy.h"
+#include "fbk_select_plan.h"
 
 namespace fbk_gquant_plan {
 
@@ -38,10 +39,7 @@ constexpr uint32_t kGlobalDigitBits = FBK_GQUANT_GLOBAL_DIGIT;
 static_assert(kLdsDigitBits >= 8 && kLdsDigitBits <= 12 && kGlobalDigitBits >= 8 && kGlobalDigitBits <= 12, "");
 
 inline constexpr uint32_t digit_bits(uint32_t path) { return path == kLds ? kLdsDigitBits : kGlobalDigitBits; }
-// fbk_sort.hip.h's key: value + 2^bit_depth in bit_depth + 1 bits up to depth 62, value ^ 2^63 in 64 bits at 63 and 64
-inline constexpr uint32_t key_bits(uint32_t bit_depth) { return bit_depth >= 63 ? 64u : bit_depth + 1; }
-// passes over the planes: ceil(key bits / digit), that is ceil((bit_depth + 1) / digit) up to depth 63 and ceil(64 / digit) at 64
-inline constexpr uint32_t passes(uint32_t bit_depth, uint32_t digit) { return (key_bits(bit_depth) + digit - 1) / digit; }
+using fbk::key_bits, fbk::passes;  // fbk_select_plan.h's key: bit_depth + 1 bits up to depth 62, else 64; ceil(key bits / digit) passes
 // Pass p takes the key's bits [pass_low(p), pass_low(p) + pass_width(p)): whole digits from the top, the SHORT digit last.  A short
 // first digit would send every column of a group to a handful of counters; in the last pass only the columns that still match a
 // request's prefix add at all.

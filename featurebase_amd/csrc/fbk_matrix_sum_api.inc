@@ -57,9 +57,7 @@ int32_t msum_enqueue(fbk_ctx* ctx, MsumPlan& p) {
   const uint32_t n_a = gf.n_a, n_b = gf.n_b;
   HIP_TRY(hipMemsetAsync(p.result.p, 0, 2 * width * 8, ctx->stream));
   KernelSpan span(ctx);
-  for (uint32_t s0 = 0; s0 < gf.n_shards; s0 += gf.chunk) {
-    const uint32_t ns = std::min(gf.chunk, gf.n_shards - s0);
-    gf.ops.densify(ctx, s0, ns);
+  if (int32_t rc = gf.ops.for_each_chunk(ctx, true, DenseOperands::Densify::together, [&](uint32_t s0, uint32_t ns) -> int32_t {
     const auto [A, B, F, S] = gf.views(s0);
     if (p.n_chunks)
       hipLaunchKernelGGL(fbk::k_msum_chunks, dim3(ns * 128u), dim3(256), 0, ctx->stream, S.arena, S.rows, ns, gf.depth, p.n_chunks, p.chunks.as<uint8_t>());
@@ -92,7 +90,8 @@ int32_t msum_enqueue(fbk_ctx* ctx, MsumPlan& p) {
 #undef FBK_MSUM
     hipLaunchKernelGGL(fbk::k_reduce_shards, dim3(uint32_t((2 * width + 255) / 256), std::min<uint32_t>(ns, 64)), dim3(256), 0, ctx->stream, p.dshard.as<u64>(), ns,
                        2 * width, p.result.as<u64>());
-  }
+    return FBK_OK;
+  })) return rc;
   HIP_TRY(hipGetLastError());
   return FBK_OK;
 }

@@ -60,9 +60,7 @@ int32_t fbk_bsi_moments(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* base_r
   HIP_TRY(hipMemsetAsync(result.p, 0, mp::kCells * 8, ctx->stream));
   {
     KernelSpan span(ctx);
-    for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-      const uint32_t ns = std::min(chunk, n_shards - s0);
-      ops.densify(ctx, s0, ns);
+    ops.for_each_chunk(ctx, true, DenseOperands::Densify::together, [&](uint32_t s0, uint32_t ns) {
       const DenseView X = ops.view(kX, s0), Y = ops.view(kY, s0), F = ops.view(kF, s0);
       const fbk::MomentsArgs args{X.arena, X.rows, Y.arena, Y.rows, F.arena, F.rows, depth_x, depth_y, ns};
       const dim3 grid(uint32_t(std::min<uint64_t>(uint64_t(ns) * units_per_shard, max_blocks)));
@@ -71,7 +69,7 @@ int32_t fbk_bsi_moments(fbk_ctx* ctx, const fbk_batch* x, const uint32_t* base_r
       else hipLaunchKernelGGL(fbk::k_bsi_moments<1>, grid, dim3(256), 0, ctx->stream, args, partial.as<long long>());
       hipLaunchKernelGGL(fbk::k_reduce_shards, dim3(mp::kCells / 256, std::min<uint32_t>(grid.x, 64)), dim3(256), 0, ctx->stream, partial.as<u64>(), grid.x,
                          uint64_t(mp::kCells), result.as<u64>());
-    }
+    });
   }
   HIP_TRY(hipGetLastError());
   int64_t cells[mp::kCells];

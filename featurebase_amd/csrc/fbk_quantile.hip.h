@@ -17,12 +17,7 @@
 
 namespace fbk {
 
-constexpr uint32_t kQuantPrefixes = 8;       // histograms of one launch: 8 * 2048 * 4 = 64 KiB of LDS at most
 constexpr uint32_t kQuantHistBlocks = 1024;  // most blocks of a launch: the partials stay within 1024 * 64 KiB = 2^26 bytes
-
-struct QuantPrefixes {
-  u64 p[kQuantPrefixes];  // ascending; entries at and past n_pre are not read
-};
 
 // part[block][j][d] = the columns of exists ∩ filter this block walked whose key has prefix pre.p[j] above bit shift + 11 and digit
 // d at bit `shift`.  n_pre == 0: no prefix yet (pass 0), one histogram of every column.  shift + 11 < 64 whenever n_pre != 0.

@@ -6,7 +6,7 @@
 // Key of a column (order preserving, unsigned): value = sign ? -magnitude : magnitude (int64 wrap-around, as k_extract_bsi);
 //   bit_depth <= 62: key = value + 2^bit_depth, bit_depth + 1 bits;  63, 64: key = value ^ 2^63, 64 bits;
 //   descending: the key's bits complemented, so "smallest key first" is the order in both directions and ties stay in ascending
-//   column order.  SortKey carries the three constants; sort_value() is the inverse.
+//   column order.  SortKey carries the three constants; sort_value() is the inverse (all in the HIP-free fbk_select_plan.h).
 // Operands are DENSE rows (k_densify_rows, a chunk of shards at a time: fbk_sort_api.inc).  One wavefront per 1024-column unit as
 // k_extract_bsi: lane p loads plane p's line, per 64-column word one in-register transpose gives lane c the magnitude of column c.
 //   k_sort_hist     radix select, most significant digit first, 11 bits per pass: the columns whose key matches the prefix chosen so
@@ -26,22 +26,11 @@
 // bits: commutes), k_extract_scan counts them, k_extract_upre adds the shards' bases.
 #pragma once
 #include "fbk_extract.hip.h"
+#include "fbk_select_plan.h"
 
 namespace fbk {
 
-constexpr uint32_t kSortDigitBits = 11;
-constexpr uint32_t kSortBins = 1u << kSortDigitBits;
 constexpr uint32_t kSortHistBlocks = 1024;  // most blocks of a k_sort_hist launch (each stores kSortBins counts)
-
-struct SortKey {
-  u64 flip;  // 2^63 in the 64-bit form, else 0
-  u64 bias;  // 2^bit_depth in the short form, else 0
-  u64 desc;  // the key's bits, if descending, else 0
-  uint32_t keep_zero;
-};
-
-__device__ __forceinline__ u64 sort_key(u64 value, const SortKey& k) { return ((value ^ k.flip) + k.bias) ^ k.desc; }
-__device__ __forceinline__ long long sort_value(u64 key, const SortKey& k) { return (long long)((((key ^ k.desc) - k.bias)) ^ k.flip); }
 
 __device__ __forceinline__ u64 sort_readlane(u64 x, uint32_t l) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)l);

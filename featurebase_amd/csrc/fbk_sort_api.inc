@@ -1,18 +1,48 @@
 // fbk_sort_api.inc — fbk_bsi_sort (Sort() by an int field) and fbk_extract_open_columns (an extract handle from a column list):
 // fbk_sort.hip.h.  Included by fbk.hip after fbk_extract_api.inc.
 //
-// fbk_bsi_sort walks the shards a few times (a radix-select pass per 11 key bits, a count pass, a collect pass).  A walk densifies
-// what is not dense a chunk of shards at a time (fbk_dense_operands.inc) under fbk_extract_*'s kExtractScratch, the filter and
-// the field in a launch each.  Device scratch (fbk.h documents it):
+// fbk_bsi_sort walks the shards a few times (a radix-select pass per 11 key bits, a count pass, a collect pass).  Its key, its cut
+// and the digit descent are fbk_select_plan.h's; its operands and its walk are FieldOperands below, which fbk_bsi_quantiles and
+// fbk_bsi_distinct_rows share.  Device scratch (fbk.h documents it):
 //   2^14 + 2^23 (histogram, the blocks' partial histograms) + 2^15 per shard (counts and prefixes of its 1024 units, key < T and
 //   key == T) + the densify chunk (<= 2^28) + 16 K (candidates) + 16 n_less + the radix sort's temporary storage (sorted pairs)
 //   + 16 n (the records) + the row lists.
 
 namespace {
 
-struct SortWalk {
-  DenseView S, F;  // the field, the filter
-  uint32_t ns, abs0;
+namespace sp = fbk_select_plan;
+
+// The operand arguments of a call over one int field and a filter row per shard, in the order these calls reject them
+int32_t field_args_ok(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_rows, uint32_t bit_depth, const fbk_batch* filter, const uint32_t* rows_f,
+                      uint32_t n_shards, uint32_t max_shards, const char* cap_text, const char* filter_text) {
+  if (bit_depth > 64) return fail(FBK_E_INVALID, "bit depth > 64");
+  if (n_shards > max_shards) return fail(FBK_E_INVALID, cap_text);
+  if (!ctx || !bsi || (n_shards && !base_rows) || (filter && n_shards && !rows_f)) return fail(FBK_E_INVALID, "NULL argument");
+  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, bsi->n_rows)) return rc;
+  return filter ? check_rows(rows_f, n_shards, filter->n_rows, filter_text) : FBK_OK;
+}
+
+// A filter row and one int field fragment per shard, the single-field sibling of GroupFieldOperands (fbk_group_field.inc): what
+// the kernels on sort_walk_unit read.  A walk densifies under kExtractScratch, the filter's rows and the field's in a launch each.
+struct FieldOperands {
+  DenseOperands ops;
+  int F = 0, S = 0;  // the operands' numbers in ops
+  uint32_t n_shards = 0;
+  // depth_read: the planes the kernels read (the fragment's exists and sign rows come with them)
+  void add(const fbk_batch* bsi, const uint32_t* base_rows, uint32_t depth_read, const fbk_batch* filter, const uint32_t* rows_f, uint32_t shards) {
+    n_shards = shards;
+    F = ops.add(filter, rows_f, 1), S = ops.add(bsi, base_rows, depth_read + 2, true);
+  }
+  int32_t upload(fbk_ctx* ctx) { return ops.upload(ctx, n_shards, sp::densify_chunk(n_shards, ops.densified_rows())); }
+
+  // fn(S, F, s0, ns, grid) for every chunk [s0, s0 + ns): the field's and the filter's views, a block per four units.  Every walk
+  // densifies again, a single chunk too: skipping the repeat (DenseOperands::for_each_chunk's first_walk) changes the launches.
+  template <class Fn>
+  void for_each_chunk(fbk_ctx* ctx, Fn fn) {
+    ops.for_each_chunk(ctx, true, DenseOperands::Densify::each, [&](uint32_t s0, uint32_t ns) {
+      fn(ops.view(S, s0), ops.view(F, s0), s0, ns, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)));
+    });
+  }
 };
 
 }  // namespace
@@ -29,54 +59,33 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
   if (out_total) *out_total = 0;
   if (flags & ~uint32_t(FBK_SORT_DESC | FBK_SORT_KEEP_ZERO)) return fail(FBK_E_INVALID, "sort: unknown flag");
   if (int32_t rc = shard_ids_ok(shard_ids, n_shards, "sort")) return rc;
-  if (n_shards > (1u << 20)) return fail(FBK_E_INVALID, "sort: at most 2^20 shards per call");
-  if (!ctx || !bsi || (filter && n_shards && !rows_f)) return fail(FBK_E_INVALID, "NULL argument");
-  if (int32_t rc = bsi_rows_ok(base_rows, n_shards, bit_depth, bsi->n_rows)) return rc;
-  if (filter)
-    if (int32_t rc = check_rows(rows_f, n_shards, filter->n_rows, "sort filter")) return rc;
+  if (int32_t rc = field_args_ok(ctx, bsi, base_rows, bit_depth, filter, rows_f, n_shards, 1u << 20, "sort: at most 2^20 shards per call", "sort filter")) return rc;
   if (n_shards == 0) return FBK_OK;
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int32_t rc = set_device(ctx)) return rc;
 
-  // the key (fbk_sort.hip.h)
-  fbk::SortKey sk{};
-  const bool wide = bit_depth >= 63;
-  const uint32_t nbits = wide ? 64 : bit_depth + 1;
-  sk.flip = wide ? 1ull << 63 : 0, sk.bias = wide ? 0 : 1ull << bit_depth;
-  sk.desc = (flags & FBK_SORT_DESC) ? (nbits == 64 ? ~0ull : (1ull << nbits) - 1) : 0;
-  sk.keep_zero = (flags & FBK_SORT_KEEP_ZERO) ? 1 : 0;
-  const uint32_t passes = (nbits + fbk::kSortDigitBits - 1) / fbk::kSortDigitBits;
+  const fbk::SortKey sk = fbk::select_key(bit_depth, flags & FBK_SORT_DESC, flags & FBK_SORT_KEEP_ZERO);
+  const uint32_t nbits = fbk::key_bits(bit_depth), passes = fbk::passes(bit_depth, fbk::kSortDigitBits);
 
-  // row lists and the densify chunk
-  DenseOperands ops;
-  const int kF = ops.add(filter, rows_f, 1), kS = ops.add(bsi, base_rows, bit_depth + 2, true);
-  const uint32_t chunk = even_chunk(n_shards, kExtractScratch, kDenseRowBytes * ops.densified_rows());
+  FieldOperands fo;
+  fo.add(bsi, base_rows, bit_depth, filter, rows_f, n_shards);
   DevBuf ids, hist, part, n_lt, n_eq, p_lt, p_eq, keys, cols, skeys, scols, tmp, ocols, ovals;
-  if (int32_t rc = ops.upload(ctx, n_shards, chunk)) return rc;
+  if (int32_t rc = fo.upload(ctx)) return rc;
   HIP_TRY(ids.alloc(ctx, uint64_t(n_shards) * 8));
   HIP_TRY(hipMemcpyAsync(ids.p, shard_ids, uint64_t(n_shards) * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hist.alloc(ctx, fbk::kSortBins * 8));
   HIP_TRY(part.alloc(ctx, uint64_t(fbk::kSortHistBlocks) * fbk::kSortBins * 4));
-  // one walk over the shards: launch(w) per chunk, everything of the chunk dense
-  auto walk = [&](auto&& launch) {
-    for (uint32_t s0 = 0; s0 < n_shards; s0 += chunk) {
-      const uint32_t ns = std::min(chunk, n_shards - s0);
-      ops.densify_one(ctx, kF, s0, ns);  // (a launch each: the filter's rows, then the field's)
-      ops.densify_one(ctx, kS, s0, ns);
-      launch(SortWalk{ops.view(kS, s0), ops.view(kF, s0), ns, s0}, dim3(extract_grid(uint64_t(ns) * fbk::kExtractUnits)));
-    }
-  };
 
   // radix select: total, then the K-th smallest key T, the columns below it and the ties to take
   std::vector<uint64_t> hh(fbk::kSortBins);
-  uint64_t total = 0, K = 0, T = 0, n_less = 0, r = 0, want = 0;
+  uint64_t total = 0, K = 0, T = 0, n_less = 0, want = 0;
   bool take_all = false;
   for (uint32_t p = 0; p < passes; ++p) {
     const uint32_t shift = fbk::kSortDigitBits * (passes - 1 - p);
     HIP_TRY(hipMemsetAsync(hist.p, 0, fbk::kSortBins * 8, ctx->stream));
-    walk([&](const SortWalk& w, dim3 grid) {
+    fo.for_each_chunk(ctx, [&](const DenseView& S, const DenseView& F, uint32_t, uint32_t ns, dim3 grid) {
       const uint32_t nb = std::min(grid.x, fbk::kSortHistBlocks);
-      hipLaunchKernelGGL(fbk::k_sort_hist, dim3(nb), dim3(256), 0, ctx->stream, w.S.arena, w.S.rows, w.F.arena, w.F.rows, w.ns, bit_depth, sk, shift, u64(T),
+      hipLaunchKernelGGL(fbk::k_sort_hist, dim3(nb), dim3(256), 0, ctx->stream, S.arena, S.rows, F.arena, F.rows, ns, bit_depth, sk, shift, u64(T),
                          p ? 1u : 0u, part.as<uint32_t>());
       hipLaunchKernelGGL(fbk::k_sort_hist_sum, dim3(fbk::kSortBins / 256, 32), dim3(256), 0, ctx->stream, part.as<uint32_t>(), nb, hist.as<u64>());
     });
@@ -90,23 +99,20 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
     if (p == 0) {
       for (uint64_t c : hh) total += c;
       if (out_total) *out_total = total;
-      const uint64_t lo = std::min(offset, total);
-      K = lo + std::min(limit, total - lo);
+      const sp::SortCut cut = sp::sort_cut(total, offset, limit);
+      K = cut.K;
       if (K >= (1ull << 31))
         return fail(FBK_E_INVALID, "sort: " + std::to_string(K) + " records to order (offset + limit, or every column without a limit); one call takes fewer than 2^31: use a limit");
-      *out_n = K - lo;
+      *out_n = K - cut.lo;
       if (*out_n > cap) return fail(FBK_E_CAPACITY, "sort: " + std::to_string(*out_n) + " records, capacity " + std::to_string(cap));
       if (*out_n == 0) return FBK_OK;
-      want = K;
-      take_all = K == total;
+      want = K, take_all = K == total;
       if (take_all) break;
     }
-    uint64_t before = 0;
-    uint32_t b = 0;
-    while (b + 1 < fbk::kSortBins && before + hh[b] < want) before += hh[b++];
-    n_less += before, want -= before, T = (T << fbk::kSortDigitBits) | b;
+    const sp::Descent d = sp::descend(hh.data(), fbk::kSortBins, want - 1);
+    n_less += d.before, want -= d.before, T = (T << fbk::kSortDigitBits) | d.bin;
   }
-  r = take_all ? 0 : want;
+  const uint64_t r = take_all ? 0 : want;
   if (take_all) n_less = K;
 
   // ranks of the candidates, then the candidates
@@ -117,8 +123,8 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
   HIP_TRY(p_eq.alloc(ctx, (n_units + 1) * 8));
   HIP_TRY(hipMemsetAsync(n_lt.as<u64>() + n_units, 0, 8, ctx->stream));
   HIP_TRY(hipMemsetAsync(n_eq.as<u64>() + n_units, 0, 8, ctx->stream));
-  walk([&](const SortWalk& w, dim3 grid) {
-    hipLaunchKernelGGL(fbk::k_sort_count, grid, dim3(256), 0, ctx->stream, w.S.arena, w.S.rows, w.F.arena, w.F.rows, w.ns, w.abs0, bit_depth, sk, u64(T),
+  fo.for_each_chunk(ctx, [&](const DenseView& S, const DenseView& F, uint32_t s0, uint32_t ns, dim3 grid) {
+    hipLaunchKernelGGL(fbk::k_sort_count, grid, dim3(256), 0, ctx->stream, S.arena, S.rows, F.arena, F.rows, ns, s0, bit_depth, sk, u64(T),
                        take_all ? 1u : 0u, n_lt.as<u64>(), n_eq.as<u64>());
   });
   size_t t_scan = 0, t_sort = 0;
@@ -133,8 +139,8 @@ int32_t fbk_bsi_sort(fbk_ctx* ctx, const fbk_batch* bsi, const uint32_t* base_ro
   HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, n_eq.as<u64>(), p_eq.as<u64>(), int(n_units + 1), ctx->stream));
   HIP_TRY(keys.alloc(ctx, K * 8));
   HIP_TRY(cols.alloc(ctx, K * 8));
-  walk([&](const SortWalk& w, dim3 grid) {
-    hipLaunchKernelGGL(fbk::k_sort_collect, grid, dim3(256), 0, ctx->stream, w.S.arena, w.S.rows, w.F.arena, w.F.rows, w.ns, w.abs0, bit_depth, sk, u64(T),
+  fo.for_each_chunk(ctx, [&](const DenseView& S, const DenseView& F, uint32_t s0, uint32_t ns, dim3 grid) {
+    hipLaunchKernelGGL(fbk::k_sort_collect, grid, dim3(256), 0, ctx->stream, S.arena, S.rows, F.arena, F.rows, ns, s0, bit_depth, sk, u64(T),
                        take_all ? 1u : 0u, p_lt.as<u64>(), p_eq.as<u64>(), ids.as<u64>(), u64(n_less), u64(r), keys.as<u64>(), cols.as<u64>());
   });
   HIP_TRY(hipGetLastError());
